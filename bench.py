@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- reads placed / s on a SARS-CoV-2-like MAT (~16M nodes).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU (for N > 1 launch with torch.distributed.run; ranks read
 RANK / LOCAL_RANK / WORLD_SIZE).  The MAT is replicated on every GPU, each rank
@@ -10,6 +10,12 @@ data-path collective; torch.distributed is used only for the timing barrier
 and the max-over-ranks reduction.  A "step" = one pass of the hot path
 (wepp_place_batch_device: both passes of the reference's per-sample loop,
 src/usher_common.cpp:386-446) over one batch of reads already resident in HBM.
+
+A plain run sets up, warms up, times the K steps and prints the headline.
+--full adds everything else the benchmark measures: the PCIe-inclusive leg, the
+whole-tree roofline run, the sensitivity ladder, the legs of the other configs,
+the tree-shape ladder and the CPU baseline.  --dump-outputs DIR writes what the
+last timed step computed as DIR/<name>.npy.
 
 Prints ONE JSON line on rank 0 (see DESIGN.md section 7 for how each field is
 obtained).
@@ -22,6 +28,7 @@ import time
 
 import numpy as np
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
@@ -79,7 +86,37 @@ def parse():
     ap.add_argument("--no-legs", action="store_true", help="skip the legs of the other configs (configs[3] shard, configs[4] "
                     "long reads, whole-genome samples) and the tree-shape ladder")
     ap.add_argument("--ladder-nodes", type=int, default=4_000_000, help="nodes of the tree-shape ladder's trees (0 disables it)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too: PCIe-inclusive leg, whole-tree roofline run, "
+                         "sensitivity ladder, legs, tree-shape ladder, CPU baseline (the options above switch them off "
+                         "one by one); a plain run does none of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (best_bfs_j, score, num_best, "
+                         "flags of every read; rank 0) as DIR/<name>.npy in float64")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # (the files of one dump stay under 64 MB)
+
+
+def dump_outputs(directory, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """Writes `arrays` (name -> one value per read) as directory/<name>.npy in float64, exact for 32-bit integers.
+    When they would take more than `limit_bytes`, a fixed sample of the reads (seed 0, ascending) is written instead,
+    and its read indices as read_index.npy."""
+    os.makedirs(directory, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    if 8 * n * len(arrays) > limit_bytes:
+        k = limit_bytes // (8 * (len(arrays) + 1))
+        idx = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+        arrays = dict({name: np.asarray(a)[idx] for name, a in arrays.items()}, read_index=idx)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a).astype(np.float64))
+
+
+def timed(fn, *a, **kw):
+    """(fn(*a, **kw), seconds it took) -- for the set-up jobs that run on worker threads"""
+    t0 = time.perf_counter()
+    return fn(*a, **kw), time.perf_counter() - t0
 
 
 def usable_cores():
@@ -393,8 +430,26 @@ def main():
             sys.exit("bench.py --gpus N>1 must be launched with python -m torch.distributed.run --nproc-per-node N")
         args.gpus = world
 
-    import torch
+    full = args.full
+    from concurrent.futures import ThreadPoolExecutor
     import wepp_amd as w
+
+    # ---- synthetic workload (identical tree on every rank, per-rank reads) ----
+    genome = args.workload == "genome"
+    long_reads = args.read_len > 400 and not genome
+    # the tree-shape ladder's host work (trees, flat images, batches, checker results) runs in background threads from
+    # the start: it is ready when the main workload has been measured
+    ladder_jobs = None
+    if full and rank == 0 and world == 1 and not args.no_legs and not args.no_crowns and args.ladder_nodes > 0:
+        ladder_pool = ThreadPoolExecutor(max_workers=3)
+        want_chk = not args.no_cpu_baseline
+        ladder_jobs = [ladder_pool.submit(ladder_prepare, w, args.ladder_nodes, label, kw, want_chk) for label, kw in LADDER]
+    # set-up jobs on worker threads (the ctypes calls release the GIL): the tree is generated while torch and the device
+    # come up, the read batches while the tree is flattened
+    setup_pool = ThreadPoolExecutor(max_workers=max(1, min(args.batches, usable_cores() // 2)))
+    tree_job = setup_pool.submit(timed, w.generate_tree, 21, args.nodes)
+
+    import torch
 
     if not torch.cuda.is_available():
         sys.exit("bench.py needs a GPU (the placement engine has no CPU fallback)")
@@ -404,19 +459,7 @@ def main():
         import torch.distributed as dist
         dist.init_process_group("nccl", device_id=dev)
 
-    # ---- synthetic workload (identical tree on every rank, per-rank reads) ----
-    genome = args.workload == "genome"
-    long_reads = args.read_len > 400 and not genome
-    t0 = time.perf_counter()
-    # the tree-shape ladder's host work (trees, flat images, batches, checker results) runs in background threads from
-    # the start: it is ready when the main workload has been measured
-    ladder_jobs = None
-    if rank == 0 and world == 1 and not args.no_legs and not args.no_crowns and args.ladder_nodes > 0:
-        from concurrent.futures import ThreadPoolExecutor
-        ladder_pool = ThreadPoolExecutor(max_workers=3)
-        want_chk = not args.no_cpu_baseline
-        ladder_jobs = [ladder_pool.submit(ladder_prepare, w, args.ladder_nodes, label, kw, want_chk) for label, kw in LADDER]
-    g = w.generate_tree(21, args.nodes)
+    g, t_tree = tree_job.result()
     amp_len, amp_step = (args.read_len, int(args.read_len * 0.85)) if long_reads else (400, 300)
     p_sub = 0.03 if long_reads else 0.001
     p_n = args.p_n if args.p_n is not None else (0.0005 if genome else 0.02 if long_reads else 0.005)
@@ -430,17 +473,19 @@ def main():
     # the timed loop rotates over N_BATCHES distinct batches, all resident in HBM (seeds 22 + 8 * rank + i: rank 0 places
     # seeds 22 .. 29): no step finds the index lines and the routing of the step before it in the caches
     seed0 = (900 if genome else 24 if long_reads else 22) + args.batches * rank
-    batches_host = [gen_reads(seed0 + i, args.reads) for i in range(args.batches)]
-    reads = batches_host[0]
-    t_gen = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    batch_jobs = [setup_pool.submit(gen_reads, seed0 + i, args.reads) for i in range(args.batches)]
     # one flatten (host), one upload (this rank's device): the C++ host flattens once per node and uploads from every
     # device thread (wepp_flat_create + wepp_mat_upload); a bench rank is its own process, so its flatten is rank-local
     # ... under torch.distributed.run every rank is a process: local rank 0 flattens and leaves the image in /dev/shm
     # (wepp_flat_save), the other ranks of the node read it back (wepp_flat_load): ONE flatten per node here too
-    t0 = time.perf_counter()
     from wepp_amd.sharding import shared_flat_image
     flat = shared_flat_image(g.tree, dist if world > 1 else None, local_rank, f"{os.environ.get('MASTER_PORT', '0')}_{args.nodes}")
     t_flat = time.perf_counter() - t0
+    batches_host = [j.result() for j in batch_jobs]
+    t_batches = time.perf_counter() - t0             # (generated beside the flatten: wall time until the last one)
+    setup_pool.shutdown()
+    reads = batches_host[0]
     t0 = time.perf_counter()
     mat = w.Mat(g.tree, device=local_rank, flat=flat)
     flat.close()
@@ -480,6 +525,7 @@ def main():
     fence()
     mat.timing_reset()
     t0 = time.perf_counter()
+    t_to_steps = t0 - T_START
     for i in range(args.steps):
         batches[i % len(batches)].place(mat, stream)
     fence()
@@ -487,16 +533,21 @@ def main():
     sweep_ms, n_launch, passes, alg_bytes = mat.last_timing()
     walk_reads, walk_iters = mat.last_walk()
     reads_timed = sum(batches[i % len(batches)].R for i in range(args.steps))
-    batch.place(mat, stream)                  # (batch 0 once more: its routing is what `streams` reports)
-    fence()
-    tiers = mat.last_tiers(R)
-    pcls, _ = mat.last_plans(R)
-    ref_out = [t.clone() for t in batch.out]
+    if args.dump_outputs and rank == 0:
+        o = [t.cpu().numpy() for t in batches[(args.steps - 1) % len(batches)].out]     # (the last timed step's batch)
+        dump_outputs(args.dump_outputs, {"best_bfs_j": o[0].view(np.uint32), "score": o[1], "num_best": o[2].view(np.uint32),
+                                         "flags": o[3].view(np.uint32)})
+    if full:
+        batch.place(mat, stream)                  # (batch 0 once more: its routing is what `streams` reports)
+        fence()
+        tiers = mat.last_tiers(R)
+        pcls, _ = mat.last_plans(R)
+        ref_out = [t.clone() for t in batch.out]
 
     # ---- SURVEY 8(d)'s metric as defined: wall clock of wepp_place_batch with HOST buffers (validation of the
     # read words, H2D of the reads, kernels, D2H of the results inside) -----------------------
     pcie = None
-    if args.pcie_steps > 0:
+    if full and args.pcie_steps > 0:
         hres = mat.place_batch(reads)                 # grows the handle's staging buffers once
         same = bool((hres.score == ref_out[1].cpu().numpy()).all() and
                     (hres.best_bfs_j == ref_out[0].cpu().numpy().view(np.uint32)).all() and
@@ -521,7 +572,7 @@ def main():
     # ---- the "HBM-roofline run" of configs[2]: same batch, work skipping off, so that
     # every tile streams the whole-tree event stream once (not part of `value`) ----
     whole = None
-    if not args.no_crowns and args.roofline_steps > 0:
+    if full and not args.no_crowns and args.roofline_steps > 0:
         mat.set_use_crowns(False)
         mat.set_use_walk(False)
         batch.place(mat, stream)
@@ -539,7 +590,7 @@ def main():
 
     # ---- sensitivity: how much of `value` is the generator's choice of |S| (rank 0 only) --------
     sens = None
-    if rank == 0 and world == 1 and not args.no_sensitivity and not args.no_crowns and not genome:
+    if full and rank == 0 and world == 1 and not args.no_sensitivity and not args.no_crowns and not genome:
         sens = []
 
         def leg(label, rd, steps=3):
@@ -570,8 +621,6 @@ def main():
                 leg(f"exactly {k} entries", truncate_reads(w, pool, k))
 
     if rank == 0:
-        gpu_res = {"score": ref_out[1].cpu().numpy(), "best": ref_out[0].cpu().numpy().view(np.uint32),
-                   "num_best": ref_out[2].cpu().numpy().view(np.uint32), "flags": ref_out[3].cpu().numpy().view(np.uint32)}
         total_reads = reads_timed * world          # (every rank places batches of the same sizes)
         value = total_reads / elapsed
         mode = "genome_samples" if genome else "long_reads" if long_reads else ("whole_tree" if (args.no_crowns and args.no_walk) else "short_reads")
@@ -588,7 +637,6 @@ def main():
                  f"N rate {p_n}; {args.batches} batches in rotation from seed {seed0}); BASELINE.json configs[4] shape on one GPU" if long_reads else
                  f"{R} synthetic ARTIC-like {args.read_len} bp reads per GPU per step (0.1 % substitutions, N rate {p_n}; "
                  f"{args.batches} distinct batches in rotation, seeds {seed0}..{seed0 + args.batches - 1}); BASELINE.json configs[2]")
-        counts = np.bincount(tiers, minlength=16)
         out = {
             "metric": "reads placed/sec on SARS-CoV-2 MAT (~16M nodes)",
             "value": value,
@@ -602,101 +650,111 @@ def main():
             "vs_baseline": None,
             "dtype": "int32",
             "data": "synthetic",
-            "value_pcie_inclusive": pcie["value"] if pcie else None,
-            "value_note": "inputs and outputs resident in HBM (wepp_place_batch_device); value_pcie_inclusive (also under "
-                          "config.pcie_inclusive_reads_per_s) is SURVEY 8(d)'s wall clock of wepp_place_batch with host buffers.  "
-                          "Both are a best case of the synthetic generator (reads of reference-like genotypes with ~1 entry): "
-                          "see `sensitivity`",
-            "pcie_inclusive": pcie,
-            "config": {
-                "pcie_inclusive_reads_per_s": pcie["value"] if pcie else None,
-                "pcie_inclusive_ms_per_step": pcie["ms_per_step"] if pcie else None,
-                "distinct_batches_in_rotation": args.batches,
-                "setup_places_every_batch_once": True,     # (device workspaces reach their size before warm-up; see the timed region)
-                "workload": f"synthetic SARS-CoV-2-like MAT N={st.n_nodes} nodes M={st.n_mutations} mutations "
-                            f"(seed 21, L=29903), {shape}",
-                "reads_per_gpu": R,
-                "read_words_per_gpu": nw,
-                "tile_reads_T": args.tile,
-                "work_skipping": not args.no_crowns,
-                "parallelism": f"read-sharded x{world}, MAT replicated, no collective",
-                "mat": {"nodes": int(st.n_nodes), "mutations": int(st.n_mutations), "events": int(st.n_events),
-                        "blocks": int(st.n_blocks), "leaves": int(st.n_leaves), "max_depth": int(st.max_depth),
-                        "device_bytes": int(st.device_bytes)},
-                "setup_s": {"generate_tree_and_batches": round(t_gen, 1), "flatten_host": round(t_flat, 1), "upload_and_handle": round(t_up, 1)},
-                "flatten": "one per node: local rank 0 flattens and shares the image through /dev/shm (wepp_flat_save / wepp_flat_load)" if world > 1
-                           else "one flatten, one upload",
-                "kernel_hash": kernel_hash(),
-            },
-            "roofline": roof,
-            "roofline_candidates": cands,
-            "walk": {"reads_walked_per_step": int(walk_reads), "wave_iterations_per_step": int(walk_iters // max(1, args.steps)),
-                     "enabled": not args.no_walk,
-                     "reads_by_plan_class": {w.PLAN_NAMES[c]: int(n) for c, n in enumerate(np.bincount(pcls, minlength=7)) if n}},
-            "streams": [{"tau": int(st.stream_tau[i]), "nodes": int(st.stream_nodes[i]), "bytes": int(st.stream_bytes_of[i]),
-                         "reads_routed": int(counts[i])} for i in range(st.n_streams)],
-            "window_crowns": {"what": "per genome window (2560 positions every 1024) the nodes a read confined to the window can be "
-                                      "placed on: out_w - in_w <= base(root) whatever it lists (the last crown of a window), and "
-                                      "out_w <= its ROOT score (the smaller ones) -- no + |S| slack as for the tree-wide streams "
-                                      "above (DESIGN.md 4.2c)",
-                              "crowns": int(st.n_window_crowns), "nodes_in_all": int(st.window_crown_nodes),
-                              "reads_routed": int(counts[w.WINDOW_CROWN_SLOT])},
-            "window_streams": {"what": "what the tiles of reads with more than 32 entries inside one genome window sweep (plan class "
-                                       "'window'; `streams` counts them under the whole tree): the window's candidate crown, or the "
-                                       "whole tree as the window sees it where no crown was built",
-                               "streams": int(st.n_window_streams), "of_which_candidate_crowns": int(st.n_window_streams_crown),
-                               "elements_in_all": int(st.window_stream_nodes),
-                               "reads_routed": int((pcls == w.PLAN_WIN).sum())},
         }
-        if whole is not None:
-            wr, wc = sweep_roofline("whole_tree", R, whole["kernel_ms_per_step"], whole["algorithmic_bytes_per_step"],
-                                    whole["stream_sweeps_per_step"], whole["steps_timed"])
-            valu = next((c for c in wc if c["bound"] == "valu_issue"), None)
-            out["roofline_whole_tree"] = {
-                "what": "same batch with work skipping and walks off: every 64-read tile streams the whole-tree event "
-                        "stream once (BASELINE.json configs[2] 'HBM-roofline run'); not part of `value`",
-                "reads_per_s": R / (whole["kernel_ms_per_step"] * 1e-3),
-                "results_identical_to_timed_run": whole["results_identical_to_timed_run"],
-                "served_from": "L2: the tiles of a launch sweep the same 1 MB chunk together (chunk-major order), so the "
-                               "algorithmic rate is an L2 rate, not an HBM rate -- it is priced against the L2 peak, and the "
-                               "kernel's binding unit is vector issue",
-                "algorithmic_gbs": wr["achieved"], "l2_peak_gbs": L2_PEAK_GBS, "frac_of_l2_peak": wr["achieved"] / L2_PEAK_GBS,
-                "algorithmic_bytes_per_step": wr["algorithmic_bytes_per_step"], "kernel_ms_per_step": wr["kernel_ms_per_step"],
-                "hbm_side_traffic_gbs": wr.get("traffic_gbs"), "hbm_side_traffic_frac_of_8TBs": wr.get("traffic_frac"),
-                "l2_hit_rate": wr.get("l2_hit_rate"), "valu_issue": valu, "provenance": wr.get("provenance")}
-        out["sensitivity"] = sens
-        # ---- the CPU checker (oracle/incremental_oracle.c) on the bench MAT: shared by the legs and the CPU baseline ----
-        ot = inc = None
-        if world == 1 and not args.no_cpu_baseline and args.cpu_baseline_seconds > 0:
-            sys.path.insert(0, os.path.join(ROOT, "tests"))
-            import oracle_bridge
-            ot = oracle_bridge.OracleTree(g.tree)
-            inc = ot.incremental()
-        # ---- the other configs of BASELINE.json on the same resident MAT (rank 0, one GPU): each leg is one GPU's share
-        # of its config, device-resident and PCIe-inclusive, with its own contract-shaped roofline ----
-        if world == 1 and not args.no_legs and not args.no_crowns and not genome and not long_reads:
-            legs = []
-            legs.append(run_leg(torch, mat, dev, stream, "configs[3]: 1.25 M 150 bp reads, one GPU's shard of the 10 M-read run", "short_reads",
-                                [g.reads(52 + i, 1_250_000, read_len=150, amplicon_len=400, amplicon_step=300, p_substitution=0.001, p_n=0.005) for i in range(4)],
-                                steps=8, pcie_steps=3, checker=inc))
-            legs.append(run_leg(torch, mat, dev, stream, "configs[4]: 125 000 reads of 1.2 kb, one GPU's shard of the 1 M-read run", "long_reads",
-                                [long_reads_batch(g, 24 + i, 125_000) for i in range(4)], steps=8, pcie_steps=3, checker=inc, n_check=128))
-            legs.append(run_leg(torch, mat, dev, stream, "whole-genome samples (the input of usher_common: read_vcf's Missing_Samples), 20 000 per step", "genome_samples",
-                                [genome_samples(g, 900 + i, 20_000) for i in range(4)], steps=8, pcie_steps=3, checker=inc, n_check=128))
-            out["legs"] = legs
-        # ---- tree-shape ladder: the default batch and 1.2 kb reads on trees of other shapes (what every number above is
-        # a best case of: median root path ~20 mutations, no polytomies) ----
-        if ladder_jobs is not None:
-            out["tree_ladder"] = {"nodes": args.ladder_nodes,
-                                  "what": "same generator, other shapes (wepp_gen_tree_params: depth_choices, p_hub, p_back_mutation); per tree "
-                                          "the crown / candidate sizes, 1 M default reads and 50 000 reads of 1.2 kb per step, first reads "
-                                          "checked against the incremental oracle",
-                                  "trees": [ladder_measure(torch, w, dev, stream, j.result()) for j in ladder_jobs]}
-            ladder_pool.shutdown()
-        if ot is not None:
-            out["cpu_baseline"] = cpu_baseline(g.tree, reads, gpu_res, args.cpu_baseline_seconds, ot, inc)
-        else:
-            out["cpu_baseline"] = None
+        config = {}
+        if full:
+            out.update({
+                "value_pcie_inclusive": pcie["value"] if pcie else None,
+                "value_note": "inputs and outputs resident in HBM (wepp_place_batch_device); value_pcie_inclusive (also under "
+                              "config.pcie_inclusive_reads_per_s) is SURVEY 8(d)'s wall clock of wepp_place_batch with host buffers.  "
+                              "Both are a best case of the synthetic generator (reads of reference-like genotypes with ~1 entry): "
+                              "see `sensitivity`",
+                "pcie_inclusive": pcie})
+            config.update({"pcie_inclusive_reads_per_s": pcie["value"] if pcie else None,
+                           "pcie_inclusive_ms_per_step": pcie["ms_per_step"] if pcie else None})
+        config.update({
+            "distinct_batches_in_rotation": args.batches,
+            "setup_places_every_batch_once": True,     # (device workspaces reach their size before warm-up; see the timed region)
+            "workload": f"synthetic SARS-CoV-2-like MAT N={st.n_nodes} nodes M={st.n_mutations} mutations "
+                        f"(seed 21, L=29903), {shape}",
+            "reads_per_gpu": R,
+            "read_words_per_gpu": nw,
+            "tile_reads_T": args.tile,
+            "work_skipping": not args.no_crowns,
+            "parallelism": f"read-sharded x{world}, MAT replicated, no collective",
+            "mat": {"nodes": int(st.n_nodes), "mutations": int(st.n_mutations), "events": int(st.n_events),
+                    "blocks": int(st.n_blocks), "leaves": int(st.n_leaves), "max_depth": int(st.max_depth),
+                    "device_bytes": int(st.device_bytes)},
+            "setup_s": {"generate_tree": round(t_tree, 1), "read_batches_beside_flatten": round(t_batches, 1),
+                        "flatten_host": round(t_flat, 1), "upload_and_handle": round(t_up, 1),
+                        "start_to_timed_steps": round(t_to_steps, 1)},
+            "flatten": "one per node: local rank 0 flattens and shares the image through /dev/shm (wepp_flat_save / wepp_flat_load)" if world > 1
+                       else "one flatten, one upload",
+            "kernel_hash": kernel_hash(),
+        })
+        out.update({"config": config, "roofline": roof, "roofline_candidates": cands})
+        if full:
+            counts = np.bincount(tiers, minlength=16)
+            out.update({
+                "walk": {"reads_walked_per_step": int(walk_reads), "wave_iterations_per_step": int(walk_iters // max(1, args.steps)),
+                         "enabled": not args.no_walk,
+                         "reads_by_plan_class": {w.PLAN_NAMES[c]: int(n) for c, n in enumerate(np.bincount(pcls, minlength=7)) if n}},
+                "streams": [{"tau": int(st.stream_tau[i]), "nodes": int(st.stream_nodes[i]), "bytes": int(st.stream_bytes_of[i]),
+                             "reads_routed": int(counts[i])} for i in range(st.n_streams)],
+                "window_crowns": {"what": "per genome window (2560 positions every 1024) the nodes a read confined to the window can be "
+                                          "placed on: out_w - in_w <= base(root) whatever it lists (the last crown of a window), and "
+                                          "out_w <= its ROOT score (the smaller ones) -- no + |S| slack as for the tree-wide streams "
+                                          "above (DESIGN.md 4.2c)",
+                                  "crowns": int(st.n_window_crowns), "nodes_in_all": int(st.window_crown_nodes),
+                                  "reads_routed": int(counts[w.WINDOW_CROWN_SLOT])},
+                "window_streams": {"what": "what the tiles of reads with more than 32 entries inside one genome window sweep (plan class "
+                                           "'window'; `streams` counts them under the whole tree): the window's candidate crown, or the "
+                                           "whole tree as the window sees it where no crown was built",
+                                   "streams": int(st.n_window_streams), "of_which_candidate_crowns": int(st.n_window_streams_crown),
+                                   "elements_in_all": int(st.window_stream_nodes),
+                                   "reads_routed": int((pcls == w.PLAN_WIN).sum())},
+            })
+            gpu_res = {"score": ref_out[1].cpu().numpy(), "best": ref_out[0].cpu().numpy().view(np.uint32),
+                       "num_best": ref_out[2].cpu().numpy().view(np.uint32), "flags": ref_out[3].cpu().numpy().view(np.uint32)}
+            if whole is not None:
+                wr, wc = sweep_roofline("whole_tree", R, whole["kernel_ms_per_step"], whole["algorithmic_bytes_per_step"],
+                                        whole["stream_sweeps_per_step"], whole["steps_timed"])
+                valu = next((c for c in wc if c["bound"] == "valu_issue"), None)
+                out["roofline_whole_tree"] = {
+                    "what": "same batch with work skipping and walks off: every 64-read tile streams the whole-tree event "
+                            "stream once (BASELINE.json configs[2] 'HBM-roofline run'); not part of `value`",
+                    "reads_per_s": R / (whole["kernel_ms_per_step"] * 1e-3),
+                    "results_identical_to_timed_run": whole["results_identical_to_timed_run"],
+                    "served_from": "L2: the tiles of a launch sweep the same 1 MB chunk together (chunk-major order), so the "
+                                   "algorithmic rate is an L2 rate, not an HBM rate -- it is priced against the L2 peak, and the "
+                                   "kernel's binding unit is vector issue",
+                    "algorithmic_gbs": wr["achieved"], "l2_peak_gbs": L2_PEAK_GBS, "frac_of_l2_peak": wr["achieved"] / L2_PEAK_GBS,
+                    "algorithmic_bytes_per_step": wr["algorithmic_bytes_per_step"], "kernel_ms_per_step": wr["kernel_ms_per_step"],
+                    "hbm_side_traffic_gbs": wr.get("traffic_gbs"), "hbm_side_traffic_frac_of_8TBs": wr.get("traffic_frac"),
+                    "l2_hit_rate": wr.get("l2_hit_rate"), "valu_issue": valu, "provenance": wr.get("provenance")}
+            out["sensitivity"] = sens
+            # ---- the CPU checker (oracle/incremental_oracle.c) on the bench MAT: shared by the legs and the CPU baseline ----
+            ot = inc = None
+            if world == 1 and not args.no_cpu_baseline and args.cpu_baseline_seconds > 0:
+                sys.path.insert(0, os.path.join(ROOT, "tests"))
+                import oracle_bridge
+                ot = oracle_bridge.OracleTree(g.tree)
+                inc = ot.incremental()
+            # ---- the other configs of BASELINE.json on the same resident MAT (rank 0, one GPU): each leg is one GPU's share
+            # of its config, device-resident and PCIe-inclusive, with its own contract-shaped roofline ----
+            if world == 1 and not args.no_legs and not args.no_crowns and not genome and not long_reads:
+                legs = []
+                legs.append(run_leg(torch, mat, dev, stream, "configs[3]: 1.25 M 150 bp reads, one GPU's shard of the 10 M-read run", "short_reads",
+                                    [g.reads(52 + i, 1_250_000, read_len=150, amplicon_len=400, amplicon_step=300, p_substitution=0.001, p_n=0.005) for i in range(4)],
+                                    steps=8, pcie_steps=3, checker=inc))
+                legs.append(run_leg(torch, mat, dev, stream, "configs[4]: 125 000 reads of 1.2 kb, one GPU's shard of the 1 M-read run", "long_reads",
+                                    [long_reads_batch(g, 24 + i, 125_000) for i in range(4)], steps=8, pcie_steps=3, checker=inc, n_check=128))
+                legs.append(run_leg(torch, mat, dev, stream, "whole-genome samples (the input of usher_common: read_vcf's Missing_Samples), 20 000 per step", "genome_samples",
+                                    [genome_samples(g, 900 + i, 20_000) for i in range(4)], steps=8, pcie_steps=3, checker=inc, n_check=128))
+                out["legs"] = legs
+            # ---- tree-shape ladder: the default batch and 1.2 kb reads on trees of other shapes (what every number above is
+            # a best case of: median root path ~20 mutations, no polytomies) ----
+            if ladder_jobs is not None:
+                out["tree_ladder"] = {"nodes": args.ladder_nodes,
+                                      "what": "same generator, other shapes (wepp_gen_tree_params: depth_choices, p_hub, p_back_mutation); per tree "
+                                              "the crown / candidate sizes, 1 M default reads and 50 000 reads of 1.2 kb per step, first reads "
+                                              "checked against the incremental oracle",
+                                      "trees": [ladder_measure(torch, w, dev, stream, j.result()) for j in ladder_jobs]}
+                ladder_pool.shutdown()
+            if ot is not None:
+                out["cpu_baseline"] = cpu_baseline(g.tree, reads, gpu_res, args.cpu_baseline_seconds, ot, inc)
+            else:
+                out["cpu_baseline"] = None
         print(json.dumps(out), flush=True)
     mat.close()
     if world > 1:

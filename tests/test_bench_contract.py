@@ -77,3 +77,56 @@ def test_bench_defaults_to_one_gpu_and_a_short_run():
         pmc = json.load(fh)
     assert {"short_reads:1000000", "short_reads:1250000", "whole_tree:1000000", "long_reads:125000", "genome_samples:20000"} <= set(pmc)
     assert all(len(e["kernel_hash"]) == len(bench.kernel_hash()) for e in pmc.values())
+
+
+def _load_bench():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_for_contract", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+def test_bench_plain_run_is_the_default_and_full_is_an_option():
+    import sys
+    bench = _load_bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"]
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 7 and a.warmup == 3
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "out"
+    finally:
+        sys.argv = argv
+
+
+def test_dump_outputs_writes_exact_float64_arrays(tmp_path):
+    import numpy as np
+    bench = _load_bench()
+    rng = np.random.default_rng(5)
+    arrays = {"best_bfs_j": rng.integers(0, 2**32, 1000, dtype=np.uint64).astype(np.uint32),
+              "score": rng.integers(-5, 40, 1000).astype(np.int32)}
+    bench.dump_outputs(str(tmp_path / "d"), arrays)
+    for name, a in arrays.items():
+        got = np.load(tmp_path / "d" / (name + ".npy"))
+        assert got.dtype == np.float64 and (got == a.astype(np.float64)).all()
+    assert not (tmp_path / "d" / "read_index.npy").exists()
+
+
+def test_dump_outputs_samples_a_large_output_the_same_way_every_time(tmp_path):
+    import numpy as np
+    bench = _load_bench()
+    a = {"score": np.arange(10_000, dtype=np.int32), "flags": np.arange(10_000, dtype=np.uint32) % 7}
+    limit = 8 * 3 * 1000                   # room for 1000 reads of two arrays + their indices
+    for d in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / d), a, limit_bytes=limit)
+    idx = np.load(tmp_path / "x" / "read_index.npy")
+    assert len(idx) == 1000 and (np.diff(idx) > 0).all()
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in os.listdir(tmp_path / "x")) <= limit + 3 * 128
+    for name in ("score", "flags", "read_index"):
+        x, y = np.load(tmp_path / "x" / (name + ".npy")), np.load(tmp_path / "y" / (name + ".npy"))
+        assert (x == y).all()
+    assert (np.load(tmp_path / "x" / "score.npy") == idx).all()
+    assert (np.load(tmp_path / "x" / "flags.npy") == idx % 7).all()
