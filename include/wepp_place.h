@@ -248,8 +248,11 @@ int wepp_mat_set_use_seeds(wepp_mat_t *mat, int enable);
 int wepp_mat_last_seeds(wepp_mat_t *mat, uint64_t *samples, uint64_t *chunks_evaluated, uint64_t *chunks_total,
                         uint64_t *most_per_sample, uint64_t *histogram8);
 
-/* Tuning knob: sub-batches wepp_place_batch cuts a batch of 65 536 reads or more into (1..8; 0 = default:
- * 4 from 262 144 reads, 2 below).  Affects speed only, never results. */
+/* Tuning knob: sub-batches wepp_place_batch cuts a batch of 65 536 reads or more into (1..8; 0 = default: one per
+ * 2 097 152 reads, rounded down, at most 8 -- and at least 2 from 524 288 reads when the handle has two or more host
+ * workers; 1 below that).  Sub-batch k runs on the handle's lane k % 2; with two or more host workers a call of several
+ * sub-batches launches them from two host threads, one per lane.  Smaller batches and calls that ask for per-node
+ * scores are never cut.  Affects speed only, never results. */
 int wepp_mat_set_pipeline(wepp_mat_t *mat, uint32_t sub_batches);
 
 /* Timing of the dominant kernel (k_sweep), measured with HIP events recorded on

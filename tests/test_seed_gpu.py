@@ -6,6 +6,7 @@ import pytest
 
 import fuzz_trees as ft
 import wepp_amd as w
+from read_kinds import far_samples
 from test_gpu_parity import assert_same
 
 pytestmark = pytest.mark.gpu
@@ -86,23 +87,9 @@ def test_second_pass_for_samples_with_many_chunks_left(oracle, monkeypatch):
     it is handed to the second pass (32 workgroups per sample, the bound shared, partials combined).  One block per
     chunk makes a 120 K-node tree 1 900 chunks; the same samples with the second pass off and against the checker."""
     monkeypatch.setenv("WEPP_SEED_CHUNK_BLOCKS", "1")
-    L = 29903
     g = w.generate_tree(33, 120000)
-    rng = np.random.default_rng(6)
-    samples = []
-    for i in range(300):                       # (more than the second pass's table holds: the overflow stays with the first)
-        k = int(rng.integers(25, 70))
-        pos = np.sort(rng.choice(np.arange(1, L + 1), size=k, replace=False))
-        ents = []
-        for p in pos:
-            ref = 1 << int(rng.integers(0, 4))
-            if rng.random() < 0.2:
-                ents.append((int(p), ref, 15, 1))
-            else:
-                a = 1 << int(rng.integers(0, 4))
-                ents.append((int(p), ref, a if a != ref else (ref << 1 if ref < 8 else 1), 0))
-        samples.append(ents)
-    reads = w.Reads.from_lists(samples)
+    # (more than the second pass's table holds: the overflow stays with the first)
+    reads = far_samples(np.random.default_rng(6), 300)
     mat = w.Mat(g.tree)
     assert mat.stats.seed_chunks > 1500
     res = mat.place_batch(reads)

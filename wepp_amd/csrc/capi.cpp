@@ -41,13 +41,13 @@ void release(wepp_mat* h) {
         }
         if (L.fork_ev) (void)hipEventDestroy(L.fork_ev);
         if (L.route_ev) (void)hipEventDestroy(L.route_ev);
+        if (L.d_seed_heavy) (void)hipFree(L.d_seed_heavy);
     }
     if (h->io_in) (void)hipFree(h->io_in);
     if (h->io_out) (void)hipFree(h->io_out);
     if (h->pin) (void)hipHostFree(h->pin);
     if (h->epp_ws) (void)hipFree(h->epp_ws);
     if (h->d_work) (void)hipFree(h->d_work);
-    if (h->d_seed_heavy) (void)hipFree(h->d_seed_heavy);
     for (uint32_t i = 0; i < wepp_mat::kRing; i++) {
         if (h->ev0[i]) (void)hipEventDestroy(h->ev0[i]);
         if (h->ev1[i]) (void)hipEventDestroy(h->ev1[i]);
@@ -378,10 +378,11 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     }
     if (e == hipSuccess) e = sweep_set_max_lds(160 * 1024);
     if (e == hipSuccess) e = seed_set_max_lds(160 * 1024);
-    if (e == hipSuccess && h->dev.seed_chunks) {
-        e = hipMalloc(&h->d_seed_heavy, seed_heavy_bytes());
-        if (e == hipSuccess) e = hipMemset(h->d_seed_heavy, 0, seed_heavy_bytes());
-    }
+    for (PlaceLane& L : h->lane)
+        if (e == hipSuccess && h->dev.seed_chunks) {
+            e = hipMalloc(&L.d_seed_heavy, seed_heavy_bytes());
+            if (e == hipSuccess) e = hipMemset(L.d_seed_heavy, 0, seed_heavy_bytes());
+        }
     if (e != hipSuccess) { release(h); return hip_fail(e, "handle setup"); }
     *out = h;
     return WEPP_OK;
@@ -478,9 +479,15 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
     return WEPP_OK;
 }
 
-// Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes (each
-// lane has its own workspace, counters, side streams and events): what they share on the handle is read-only here but
-// for the event ring (a slot claimed atomically), the job-size hint (atomic) and the call statistics (stat_mu).
+// Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes, and
+// even with one host thread their kernels may overlap on the device (each lane has its own compute stream).  Each lane
+// has its own workspace, routing counters, side streams, events and k_seed second-pass table.  What they share on the
+// handle:
+//   - the tree and everything built from it (read-only here);
+//   - the event ring (a slot claimed atomically);
+//   - the hints job_events and ww_by_jobs (atomics; they choose how the next call cuts its work, never its results);
+//   - the call statistics (stat_mu) and the device counters d_work (device atomics, summed over both lanes);
+//   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
 int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
                  uint32_t* d_best_bfs_j, int32_t* d_score, uint32_t* d_num_best, uint32_t* d_flags, hipStream_t stream,
                  uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx = 0) {
@@ -1073,7 +1080,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (fork) HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
         if (debug_plans) fprintf(stderr, "[plan] seed count=%u maxk=%u chunks=%u lds=%u\n", seed_n, seed_maxk, mat->dev.seed_chunks, seed_lds_bytes(mat->dev, cap));
         HIP_TRY(launch_seed(mat->dev, mat->streams.back(), list + seed_off, seed_n, cap, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score,
-                            d_num_best, d_flags, mat->d_work, tun.seed_heavy ? mat->d_seed_heavy : nullptr, q));
+                            d_num_best, d_flags, mat->d_work, tun.seed_heavy ? L.d_seed_heavy : nullptr, q));
         if (fork) {
             HIP_TRY(hipEventRecord(L.join_ev[OTHER_SIDE_STREAMS - 2], q));
             bool listed = false;
