@@ -371,7 +371,16 @@ int wepp_gen_reads_destroy(wepp_gen_reads_t *r);
  * Output: the mutations mapper_body would add (:145-156), as (row, node id,
  * par_nuc mask, mut_nuc mask), rows in order and BFS order inside a row.
  * *n_out receives their number; WEPP_ELIMIT (with *n_out set) when capacity is
- * too small.  Limits: tree depth <= 140, < 2^28 nodes. */
+ * too small: nothing is then written to the output arrays, and never more than
+ * `capacity` entries are.
+ * The var_node of a row may come in any order; a node named more than once in a
+ * row keeps its LAST entry (:48-63); node ids need not follow any traversal
+ * order (the root need not be 0, a parent may have a larger id than its child).
+ * Limits: < 2^28 nodes.  A tree of any depth is accepted as long as every
+ * observed allele set is non-empty and no node has more than 32767 children
+ * (the level-synchronous kernels); rows with an empty allele set, or a larger
+ * polytomy, need the kernels with an LDS stack: tree depth <= 140, else
+ * WEPP_ELIMIT from the run (the plan stays usable). */
 int wepp_fitch_sites(const wepp_tree_desc *tree, int device, uint32_t n_sites, const uint8_t *site_ref,
                      const uint32_t *var_off, const uint32_t *var_node, const uint8_t *var_nuc,
                      uint64_t capacity, uint64_t *n_out, uint32_t *out_site, uint32_t *out_node,
@@ -390,6 +399,13 @@ int wepp_fitch_plan_destroy(wepp_fitch_plan_t *plan);
 /* wall time of the calling thread's last wepp_fitch_plan_run by phase (ms): host preparation of the rows, uploads,
  * kernels, sort + decode + copy-out of the mutations */
 int wepp_fitch_last_timing(double *prep_ms, double *upload_ms, double *kernels_ms, double *output_ms);
+/* debug query: what the calling thread's last wepp_fitch_plan_run that reached the kernels did.  form = one of
+ * WEPP_FITCH_FORM_* (-1 before any run), chunks = DFS chunks of the stack forms (0 for the level form), groups = how
+ * many groups of batches the rows were cut into, duplicates_dropped = 1 when some row named a node more than once */
+#define WEPP_FITCH_FORM_LEVELS 0
+#define WEPP_FITCH_FORM_SETS 1
+#define WEPP_FITCH_FORM_SCORES 2
+int wepp_fitch_last_run_info(int *form, uint32_t *chunks, uint32_t *groups, int *duplicates_dropped);
 
 /* ---- WEPP's own read placement: EPP sets and haplotype scores -------------- *
  * Replaces wepp_filter::cartesian_map (src/WEPP/initial_filter.cpp:140-239) with

@@ -7,7 +7,8 @@ WEPP_IX_PRE_MIN_NODES=0): the three paths whose speeds are quoted at 16 M nodes,
  (b) WEPP's own placer (wepp_epp_map, src/WEPP/initial_filter.cpp:41-239): per-read outputs of a 20 000-read call for
      300+ reads against oracle_epp_map, every output of a call on those reads, run-to-run identity of the big call;
  (c) per-site Fitch-Sankoff (wepp_fitch_plan_run, src/usher_mapper.cpp:7-162) on the 16 M-node topology: 64 rows
-     against oracle_mapper_body.
+     (leaves and ~1 % internal nodes, in shuffled order, ~1 % of the nodes named twice with different masks) against
+     oracle_mapper_body.
 Prints one JSON line; exits non-zero on a mismatch."""
 import json
 import os
@@ -116,16 +117,34 @@ def main():
         leaves = np.flatnonzero(~has_child).astype(np.uint32)
         rng = np.random.default_rng(5)
         rows = int(os.environ.get("FULL_FITCH_ROWS", "64"))
-        per = max(1, int(len(leaves) * 0.002))
+        internal = np.flatnonzero(has_child).astype(np.uint32)
+        per_leaf = max(1, int(len(leaves) * 0.002))
+        per_int = max(1, per_leaf // 100)                  # ~1 % of a row's nodes are internal nodes
+        per_dup = max(1, (per_leaf + per_int) // 100)      # ~1 % of them are named twice, with different masks
+        per = per_leaf + per_int + per_dup
         site_ref = (1 << rng.integers(0, 4, rows)).astype(np.uint8)
         var_off = (np.arange(rows + 1, dtype=np.uint64) * per).astype(np.uint32)
-        var_node = np.concatenate([rng.choice(leaves, per, replace=False) for _ in range(rows)]).astype(np.uint32)
-        var_nuc = (1 << rng.integers(0, 4, rows * per)).astype(np.uint8)
-        amb = rng.random(rows * per) < 0.05
-        var_nuc[amb] |= (1 << rng.integers(0, 4, int(amb.sum()))).astype(np.uint8)
+        nodes, nucs = [], []
+        for _ in range(rows):
+            nd_ = np.concatenate([rng.choice(leaves, per_leaf, replace=False), rng.choice(internal, per_int, replace=False)])
+            nc_ = (1 << rng.integers(0, 4, len(nd_))).astype(np.uint8)
+            amb = rng.random(len(nd_)) < 0.05
+            nc_[amb] |= (1 << rng.integers(0, 4, int(amb.sum()))).astype(np.uint8)
+            again = rng.choice(len(nd_), per_dup, replace=False)
+            other = ((nc_[again] << 1) | (nc_[again] >> 3)) & 15          # the same bits rotated: never the same mask
+            same_mask = other == nc_[again]                               # (only 15 rotates onto itself)
+            other[same_mask] = 1
+            nd_, nc_ = np.concatenate([nd_, nd_[again]]), np.concatenate([nc_, other.astype(np.uint8)])
+            order = rng.permutation(len(nd_))                             # file order: unsorted, the later entry wins
+            nodes.append(nd_[order]); nucs.append(nc_[order])
+        var_node = np.concatenate(nodes).astype(np.uint32)
+        var_nuc = np.concatenate(nucs).astype(np.uint8)
+        assert (var_nuc != 0).all()
         bare = w.Tree(tree.parent, np.zeros(n + 1, np.uint32), [], [], [])
         plan = w.FitchPlan(bare)
         s, nd, par, mut = plan.run(site_ref, var_off, var_node, var_nuc, capacity=int(1.3 * rows * per + rows))
+        info = w.fitch_last_run_info()
+        assert info["form"] == "levels" and info["duplicates_dropped"], info
         plan.close()
         ob = oracle_bridge.OracleTree(bare)
 
@@ -145,7 +164,8 @@ def main():
             k += len(want)
         assert k == len(s), (k, len(s))
         ob.close()
-        out["fitch"] = {"rows": rows, "observations_per_row": per, "mutations": int(len(s)), "oracle_s": round(t_or, 1),
+        out["fitch"] = {"rows": rows, "observations_per_row": per, "internal_observations_per_row": per_int,
+                        "duplicates_per_row": per_dup, "mutations": int(len(s)), "oracle_s": round(t_or, 1),
                         "seconds": round(time.perf_counter() - t1, 1)}
     ot.close()
     mat.close()

@@ -167,6 +167,8 @@ _SIGS = {
                                            ctypes.POINTER(ctypes.c_uint64), _V, _V, _V, _V]),
     "wepp_fitch_plan_destroy": (ctypes.c_int, [_V]),
     "wepp_fitch_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
+    "wepp_fitch_last_run_info": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint32),
+                                               ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int)]),
     "wepp_epp_map": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.c_uint32,
                                     ctypes.POINTER(EppOutC)]),
     "wepp_epp_fetch_lists": (ctypes.c_int, [_V, _V, ctypes.c_uint64]),

@@ -292,6 +292,18 @@ def fitch_last_timing():
     return dict(prep_ms=d[0].value, upload_ms=d[1].value, kernels_ms=d[2].value, output_ms=d[3].value)
 
 
+FITCH_FORMS = ("levels", "sets", "scores")
+
+
+def fitch_last_run_info():
+    """What this thread's last Fitch-Sankoff run did: form ("levels", "sets", "scores"; None before any run), DFS
+    chunks (0 in the level form), groups of batches, whether a row named a node more than once."""
+    form, chunks, groups, dups = ctypes.c_int(), ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_int()
+    check(lib.wepp_fitch_last_run_info(ctypes.byref(form), ctypes.byref(chunks), ctypes.byref(groups), ctypes.byref(dups)))
+    return dict(form=FITCH_FORMS[form.value] if form.value >= 0 else None, chunks=int(chunks.value),
+                groups=int(groups.value), duplicates_dropped=bool(dups.value))
+
+
 class FitchPlan:
     """wepp_fitch_plan_*: the tree-dependent part of the Fitch-Sankoff pass, done once."""
 

@@ -41,7 +41,19 @@ struct DevBuf {
 namespace {
 thread_local double g_fitch_ms[4] = {0, 0, 0, 0};     // host preparation of the rows, uploads, kernels, sort + decode + copy-out
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+// what the calling thread's last run did: the form it chose, its chunks and groups, whether a row named a node twice
+thread_local int g_fitch_form = -1;
+thread_local uint32_t g_fitch_chunks = 0, g_fitch_groups = 0;
+thread_local int g_fitch_dups = 0;
 }  // namespace
+
+extern "C" int wepp_fitch_last_run_info(int* form, uint32_t* chunks, uint32_t* groups, int* duplicates_dropped) {
+    if (form) *form = g_fitch_form;
+    if (chunks) *chunks = g_fitch_chunks;
+    if (groups) *groups = g_fitch_groups;
+    if (duplicates_dropped) *duplicates_dropped = g_fitch_dups;
+    return WEPP_OK;
+}
 
 extern "C" int wepp_fitch_last_timing(double* prep_ms, double* upload_ms, double* kernels_ms, double* output_ms) {
     if (prep_ms) *prep_ms = g_fitch_ms[0];
@@ -64,7 +76,37 @@ struct wepp_fitch_plan {
     DevBuf d_meta, d_cs, d_cd, d_cm, d_co, d_lcoff, d_lpar, d_b2i, d_tables, d_id2bfs, d_id2dfs;
     size_t tables_bytes = 0;
     bool dev_topology = false, dev_levels = false, dev_b2i = false;
+    void build_chunks();
 };
+
+// chunks of consecutive DFS nodes (one wave each) and what is open at their boundaries: only the two stack forms
+// use them, so they are built on the first run that selects one (as the level tables are on theirs)
+void wepp_fitch_plan::build_chunks() {
+    D = f.max_depth + 1;
+    C = std::max<uint32_t>(1, std::min<uint32_t>(256, N / 2048));
+    if (const char* env = std::getenv("WEPP_FITCH_CHUNKS"))      // test hook: force the number of chunks
+        C = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)std::atoi(env), N));
+    chunk_start.assign(C + 1, 0); chunk_depth.assign(C + 1, 0); chunk_min.assign(C, 0); chunk_open.assign((size_t)(C + 1) * D, 0);
+    for (uint32_t c = 0; c <= C; c++) chunk_start[c] = (uint32_t)((uint64_t)N * c / C);
+    for (uint32_t c = 0; c <= C; c++) {
+        // nodes open before node a (c < C): its strict ancestors; after the last node: the
+        // strict ancestors of that leaf (the single node itself when the tree is one node)
+        uint32_t x;
+        if (c < C) { x = chunk_start[c]; chunk_depth[c] = depth[x]; }
+        else if (N == 1) { chunk_depth[c] = 1; chunk_open[(size_t)c * D] = 0; continue; }
+        else { x = N - 1; chunk_depth[c] = depth[x]; }
+        uint32_t anc = x;
+        for (uint32_t k = chunk_depth[c]; k-- > 0;) {
+            anc = f.parent_dfs[anc];
+            chunk_open[(size_t)c * D + k] = anc;
+        }
+    }
+    for (uint32_t c = 0; c < C; c++) {
+        uint32_t mn = 0xFFFFFFFFu;
+        for (uint32_t d = chunk_start[c]; d < chunk_start[c + 1]; d++) mn = std::min(mn, depth[d]);
+        chunk_min[c] = mn;
+    }
+}
 
 extern "C" int wepp_fitch_plan_create(const wepp_tree_desc* tree, int device, wepp_fitch_plan_t** out) {
     if (!tree || !out) return set_error(WEPP_EINVAL, "null argument");
@@ -87,9 +129,6 @@ extern "C" int wepp_fitch_plan_create(const wepp_tree_desc* tree, int device, we
     }
     const uint32_t N = f.N;
     if (N >= (1u << 28)) return set_error(WEPP_ELIMIT, "more than 2^28 nodes");
-    if (f.max_depth > FITCH_MAX_DEPTH)
-        return set_error(WEPP_ELIMIT, "tree depth " + std::to_string(f.max_depth) + " exceeds the LDS stack (" +
-                                          std::to_string(FITCH_MAX_DEPTH) + ")");
     std::vector<uint32_t>&meta = plan->meta, &id2dfs = plan->id2dfs, &depth = plan->depth;
     meta.assign(N, 0); id2dfs.assign(N, 0); depth.assign(N, 0);
     std::vector<uint32_t> nchild(N, 0);
@@ -102,36 +141,7 @@ extern "C" int wepp_fitch_plan_create(const wepp_tree_desc* tree, int device, we
         meta[d] = depth[d] | ((f.nstat[d] & NS_LEAF) ? 0x80000000u : 0u);
         id2dfs[f.dfs2id[d]] = d;
     }
-    // chunks of consecutive DFS nodes (one wave each) and what is open at their boundaries
-    const uint32_t D = f.max_depth + 1;
-    uint32_t C = std::max<uint32_t>(1, std::min<uint32_t>(256, N / 2048));
-    if (const char* env = std::getenv("WEPP_FITCH_CHUNKS"))      // test hook: force the number of chunks
-        C = std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)std::atoi(env), N));
-    std::vector<uint32_t>&chunk_start = plan->chunk_start, &chunk_depth = plan->chunk_depth, &chunk_min = plan->chunk_min,
-                         &chunk_open = plan->chunk_open;
-    chunk_start.assign(C + 1, 0); chunk_depth.assign(C + 1, 0); chunk_min.assign(C, 0); chunk_open.assign((size_t)(C + 1) * D, 0);
-    for (uint32_t c = 0; c <= C; c++) chunk_start[c] = (uint32_t)((uint64_t)N * c / C);
-    for (uint32_t c = 0; c <= C; c++) {
-        // nodes open before node a (c < C): its strict ancestors; after the last node: the
-        // strict ancestors of that leaf (the single node itself when the tree is one node)
-        uint32_t x;
-        if (c < C) { x = chunk_start[c]; chunk_depth[c] = depth[x]; }
-        else if (N == 1) { chunk_depth[c] = 1; chunk_open[(size_t)c * D] = 0; continue; }
-        else { x = N - 1; chunk_depth[c] = depth[x]; }
-        uint32_t anc = x;
-        for (uint32_t k = chunk_depth[c]; k-- > 0;) {
-            anc = f.parent_dfs[anc];
-            chunk_open[(size_t)c * D + k] = anc;
-        }
-    }
-    for (uint32_t c = 0; c < C; c++) {
-        uint32_t mn = 0xFFFFFFFFu;
-        for (uint32_t d = chunk_start[c]; d < chunk_start[c + 1]; d++) mn = std::min(mn, depth[d]);
-        chunk_min[c] = mn;
-    }
     plan->N = N;
-    plan->D = D;
-    plan->C = C;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return set_error(WEPP_EDEVICE, "no HIP device available (the Fitch-Sankoff pass has no CPU fallback)");
@@ -157,7 +167,7 @@ extern "C" int wepp_fitch_plan_run(wepp_fitch_plan_t* plan, uint32_t n_sites, co
     if (n_sites == 0) return WEPP_OK;
     const int device = plan->device;
     FlatMAT& f = plan->f;
-    const uint32_t N = plan->N, D = plan->D, C = plan->C;
+    const uint32_t N = plan->N;
     const double t_begin = now_ms();
     std::vector<uint32_t>&meta = plan->meta, &id2dfs = plan->id2dfs, &depth = plan->depth, &chunk_start = plan->chunk_start,
                          &chunk_depth = plan->chunk_depth, &chunk_min = plan->chunk_min, &chunk_open = plan->chunk_open;
@@ -177,6 +187,19 @@ extern "C" int wepp_fitch_plan_run(wepp_fitch_plan_t* plan, uint32_t n_sites, co
     bool levels = sets_ok;
     if (const char* env = std::getenv("WEPP_FITCH_DFS"))          // test hook: force the DFS stack forms
         if (env[0] == '1') levels = false;
+    // only the stack forms have a stack: the level form takes a tree of any depth (one launch pair per level)
+    if (!levels && f.max_depth > FITCH_MAX_DEPTH)
+        return set_error(WEPP_ELIMIT, "tree depth " + std::to_string(f.max_depth) + " exceeds the LDS stack (" +
+                                          std::to_string(FITCH_MAX_DEPTH) + ") of the form these rows need");
+    if (!levels && chunk_start.empty()) {
+        try {
+            plan->build_chunks();
+        } catch (const std::bad_alloc&) {
+            chunk_start.clear();                                   // built again by the next run that needs them
+            return set_error(WEPP_ENOMEM, "out of host memory while building the chunk tables");
+        }
+    }
+    const uint32_t D = plan->D, C = plan->C;
     std::vector<uint8_t> ref_idx(n_sites);
     for (uint32_t s2 = 0; s2 < n_sites; s2++) {
         const uint8_t r = site_ref[s2] & 15;
@@ -222,7 +245,9 @@ extern "C" int wepp_fitch_plan_run(wepp_fitch_plan_t* plan, uint32_t n_sites, co
     // (the decision tables the plan already holds are part of what a run may use: without them in the sum every run
     // after the first saw half the memory and cut its rows into twice as many groups)
     const size_t budget = (free_b + plan->tables_bytes) / 2;
-    const uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nbatches, budget / std::max<size_t>(per_batch, 1)));
+    uint32_t group = (uint32_t)std::max<size_t>(1, std::min<size_t>(nbatches, budget / std::max<size_t>(per_batch, 1)));
+    if (const char* env = std::getenv("WEPP_FITCH_GROUP"))        // test hook: at most this many batches per group
+        group = std::max<uint32_t>(1, std::min<uint32_t>(group, (uint32_t)std::atoi(env)));
     // per-call buffers; the decision tables (tens of GB at 16 M nodes) and the topology stay with the plan
     const size_t tables_need = (size_t)N * rows_per_batch * group;
     if (tables_need > plan->tables_bytes) {
@@ -237,7 +262,7 @@ extern "C" int wepp_fitch_plan_run(wepp_fitch_plan_t* plan, uint32_t n_sites, co
         (e = d_inh.alloc(part_bytes * group)) != hipSuccess || (e = d_outp.alloc(part_bytes * group)) != hipSuccess ||
         (e = d_count.alloc(8)) != hipSuccess || (e = d_out.alloc(std::max<uint64_t>(capacity, 1) * 8)) != hipSuccess)
         return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    if (!plan->dev_topology) {
+    if (!levels && !plan->dev_topology) {
         if ((e = d_meta.alloc((size_t)N * 4)) != hipSuccess || (e = d_cs.alloc((C + 1) * 4)) != hipSuccess ||
             (e = d_cd.alloc((C + 1) * 4)) != hipSuccess || (e = d_cm.alloc(C * 4)) != hipSuccess ||
             (e = d_co.alloc(chunk_open.size() * 4)) != hipSuccess)
@@ -286,7 +311,11 @@ extern "C" int wepp_fitch_plan_run(wepp_fitch_plan_t* plan, uint32_t n_sites, co
         if (e == hipErrorInvalidValue) { (void)hipGetLastError(); return set_error(WEPP_EINVAL, "var_node out of range"); }
         if (e != hipSuccess) return hipf(e, "preparation of the rows");
         if (!in_b) { keys_final = d_vdfs2.as<uint32_t>(); nuc_final = d_vnuc2.as<uint8_t>(); }
+        g_fitch_dups = in_b ? 0 : 1;
     }
+    g_fitch_form = levels ? WEPP_FITCH_FORM_LEVELS : sets_ok ? WEPP_FITCH_FORM_SETS : WEPP_FITCH_FORM_SCORES;
+    g_fitch_chunks = levels ? 0 : C;
+    g_fitch_groups = (nbatches + group - 1) / group;
     const double t_up = now_ms();
     FitchLevels fl{N, levels ? (uint32_t)level_off.size() - 1 : 0, d_lcoff.as<uint32_t>(), d_lpar.as<uint32_t>()};
     FitchTree ft{N, f.max_depth, C, d_meta.as<uint32_t>(), d_cs.as<uint32_t>(), d_cd.as<uint32_t>(),
