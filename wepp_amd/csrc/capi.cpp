@@ -485,7 +485,7 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
 // handle:
 //   - the tree and everything built from it (read-only here);
 //   - the event ring (a slot claimed atomically);
-//   - the hints job_events and ww_by_jobs (atomics; they choose how the next call cuts its work, never its results);
+//   - the hints job_events, ww_by_jobs and expect_jobs8 (atomics; they choose how the next call cuts its work, never its results);
 //   - the call statistics (stat_mu) and the device counters d_work (device atomics, summed over both lanes);
 //   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
 int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
@@ -599,10 +599,20 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // join the caller's stream at the end.
     const bool walking = mat->use_walk && walk_max_events;
     hipStream_t ps = walking ? L.side[PLAN_STREAM] : stream;
+    // WEPP_STEP_UNFUSED=1 (A/B aid): the launches behind k_route as they were before k_step -- the plain walks, k_walk_wave
+    // on a side stream, the 8-entry job class blind on another, forked from an event of their own; results are identical
+    const bool step_unfused = tun.step_unfused;
+    // what the side streams of a call wait for: the event behind k_route.  The timing event of the call's ring slot is
+    // recorded there anyway and serves (a second record cost a call into the runtime per step).
+    const hipEvent_t fork_from = step_unfused ? L.route_ev : mat->ev0[ev_slot];
+    // the 8-entry job class (reads with more events than a wave pass takes): launched blind behind k_route only when the
+    // handle's previous call held such reads -- two launches that find nothing, a fork and a join otherwise --, else from
+    // the counters like the 16-entry class.  A hint: a call it misleads launches the class late and places every read.
+    const bool jobs8_blind = step_unfused || mat->expect_jobs8.load(std::memory_order_relaxed) != 0;
     // one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
     auto blind_class = [&](uint32_t cls, hipStream_t q, bool fork_q) -> hipError_t {
         hipError_t e = hipSuccess;
-        if (fork_q) e = hipStreamWaitEvent(q, L.route_ev, 0);
+        if (fork_q) e = hipStreamWaitEvent(q, fork_from, 0);
         if (e != hipSuccess) return e;
         if (cls == PLAN_WALK8 || cls == PLAN_WALK16) {
             e = launch_walk_blind(mat->dev, cls, cls == PLAN_WALK8 ? stack8 : stack16, n_reads, wlist[cls], tier_info + TI_WCUR + cls, d_read_off, d_read_word,
@@ -642,26 +652,33 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         L.info_idx ^= 1u;
         HIP_TRY(hipEventRecord(mat->ev0[ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
         if (walking) {
-            HIP_TRY(hipEventRecord(L.route_ev, stream));
-            // Launched BLIND, sized for the worst case, before the routing counters are back: the two classes of reads with
-            // at most WALK8_K entries -- nearly every read of a sequencing run.  The plain walks go on the caller's stream, right
-            // behind k_route (no cross-stream wait: ~25 us); on a side stream the reads with many events, a wave each, and
-            // the chunked class (reads with even more events, cut into jobs: k_route has entered them into a job table; walk +
-            // combination leave at once when the class outgrew the table, TI_JOVER: the host's planned launch takes it).  The classes of 9 - 16 entries are launched from the
-            // same tables once the counters say they hold reads (blind_class below): two launches sized for a million
-            // reads that find a handful cost ~20 us of workgroup dispatch each, and eight API calls per device call.
-            HIP_TRY(blind_class(PLAN_WALK8, stream, false));
-            {   // the reads with many events, a wave per 64 of them (wave_kernels.hip), then what is left of the chunked class
+            if (step_unfused) HIP_TRY(hipEventRecord(L.route_ev, stream));
+            // Launched BLIND, sized for the worst case, before the routing counters are back: the plain walkers of at most
+            // WALK8_K entries -- nearly every read of a sequencing run -- and the reads with many events, a wave per 64 of them
+            // (place_dev.hpp), in ONE launch on the caller's stream, right behind k_route (no cross-stream wait: ~15 - 30 us):
+            // k_step's workgroups take their role from k_route's counters on the device.  The chunked class (reads with even
+            // more events, cut into jobs: k_route has entered them into a job table; walk + combination leave at once when
+            // the class outgrew the table, TI_JOVER: the host's planned launch takes it) goes blind on a side stream when the
+            // handle expects such reads.  The classes of 9 - 16 entries are launched from the same tables once the counters
+            // say they hold reads (blind_class below): two launches sized for a million reads that find a handful cost
+            // ~20 us of workgroup dispatch each, and eight API calls per device call.
+            if (step_unfused) {
+                HIP_TRY(blind_class(PLAN_WALK8, stream, false));
                 hipStream_t q = L.side[MAX_STREAMS - 1];
-                HIP_TRY(hipStreamWaitEvent(q, L.route_ev, 0));
+                HIP_TRY(hipStreamWaitEvent(q, fork_from, 0));
                 HIP_TRY(launch_walk_wave(mat->dev, wwlist, tier_info + TI_WWCUR, n_reads, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best,
                                          d_flags, mat->d_work, wsid, q));
                 HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 1], q));
-                // (the job class on a stream of its own: nearly always two launches that find nothing, ~10 us that
-                // used to sit behind the wave kernel on the call's longest chain)
+            } else {
+                // (wwlist also takes the few walkers of 9 - 16 entries k_route moves there, TI_W16WAVE, whatever the hint
+                // ww_by_jobs says: k_step reads the lists' cursors, and is the plain blind walk when they are empty)
+                HIP_TRY(launch_step(mat->dev, stack8, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
+                                    d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream));
+            }
+            if (jobs8_blind) {
+                // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
                 hipStream_t q2 = L.side[MAX_STREAMS - 2];
-                HIP_TRY(hipStreamWaitEvent(q2, L.route_ev, 0));
-                HIP_TRY(blind_class(PLAN_WALKC8, q2, false));
+                HIP_TRY(blind_class(PLAN_WALKC8, q2, true));
                 HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 2], q2));
             }
             if (tun.blind16) {
@@ -670,7 +687,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                 HIP_TRY(blind_class(PLAN_WALK16, L.side[BLIND16_STREAM], true));
                 HIP_TRY(hipEventRecord(L.join_ev[BLIND16_STREAM], L.side[BLIND16_STREAM]));
             }
-            HIP_TRY(hipStreamWaitEvent(ps, L.route_ev, 0));
+            HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
         }
         HIP_TRY(launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps));
         return WEPP_OK;
@@ -700,6 +717,10 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (q != hipSuccess) HIP_TRY(hipStreamSynchronize(ps));
     }
     const uint32_t* info = L.h_info;
+    if (tun.debug_plans)
+        fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
+                n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
+                info[TI_CCUR + 1], info[TI_JCUR], info[TI_JCUR + 1], info[TI_JOVER], info[TI_JOVER + 1]);
     for (uint32_t cc = 0; cc < 2; cc++) {
         const uint64_t ev = (uint64_t)info[TI_EVENTS + cc] << 6;
         const uint32_t je = (uint32_t)std::min<uint64_t>(WALK_JOB_EVENTS_MAX, std::max<uint64_t>(WALK_JOB_EVENTS, ev / WALK_TARGET_JOBS));
@@ -712,8 +733,12 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         mat->ww_by_jobs.store((info[TI_WWCAND] > WW_CALL_MAX_SMALL * scale || info[TI_WWCAND + 1] > WW_CALL_MAX_BIG * scale) ? 1u : 0u, std::memory_order_relaxed);
     }
     const bool blind_walks = mat->use_walk && walk_max_events;       // (launched behind k_route, joined below)
-    bool late16[2] = {false, false};
+    bool late16[2] = {false, false}, late8 = false;
     if (blind_walks) {
+        // the 8-entry job class when the hint did not expect it, and the hint of the next call
+        const bool jobs8 = info[TI_CCUR] && !info[TI_JOVER];
+        if (jobs8 && !jobs8_blind) { HIP_TRY(blind_class(PLAN_WALKC8, L.side[MAX_STREAMS - 2], true)); HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 2], L.side[MAX_STREAMS - 2])); late8 = true; }
+        mat->expect_jobs8.store(jobs8 ? 1u : 0u, std::memory_order_relaxed);
         // the classes of 9 - 16 entries, from k_route's tables like the others, when they hold reads
         if (tun.blind16) late16[0] = true;
         else if (info[TI_WCUR + 1]) { HIP_TRY(blind_class(PLAN_WALK16, L.side[BLIND16_STREAM], true)); HIP_TRY(hipEventRecord(L.join_ev[BLIND16_STREAM], L.side[BLIND16_STREAM])); late16[0] = true; }
@@ -1120,8 +1145,8 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         // the plan stream and the blind walks' side streams join the caller's stream
         HIP_TRY(hipEventRecord(L.join_ev[PLAN_STREAM], ps));
         HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[PLAN_STREAM], 0));
-        HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 1], 0));
-        HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 2], 0));
+        if (step_unfused) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 1], 0));
+        if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 2], 0));
         if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[BLIND16_STREAM], 0));
         if (late16[1]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 3], 0));
     }

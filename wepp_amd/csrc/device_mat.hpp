@@ -206,6 +206,17 @@ hipError_t launch_finalize_jobs(const DevMAT& m, const uint32_t* list, uint32_t 
 hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_t* count, uint32_t n_reads, const uint32_t* d_read_off,
                             const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
                             uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
+// wave-role workgroups of k_step (WALK_WAVES waves each) at the most: beyond, they loop over the reads with many events.
+// A million reads of a sequencing run hold ~300 reads with more than 64 events (a workgroup each) and ~3 700 smaller ones
+// (a wave each): ~2 150 workgroups.  With 1 024 the workgroups of the large reads took small ones behind them, on the
+// step's longest chain.
+constexpr uint32_t STEP_WAVE_WGS = 2560;
+// the two common classes of a call in one launch sized BLIND (k_step): the plain walkers wlist[0 .. *wcount) of up to
+// WALK8_K entries as launch_walk_blind places them, and -- wwlist != nullptr -- the reads with many events as
+// launch_walk_wave places them (wwcount = its two cursors), in the first workgroups
+hipError_t launch_step(const DevMAT& m, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
+                       const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
+                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
 // a chunked class sized blind: jobs[0 .. *n_jobs) (k_route's table), partials into jb.part_*, then the combination over
 // clist[0 .. *n_class); both leave at once when *jb.skip != 0
 hipError_t launch_walk_jobs_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, const WalkJobs& jb, const uint32_t* jobs, const uint32_t* n_jobs,

@@ -161,6 +161,331 @@ __device__ __forceinline__ void emit_result(const DevMAT& m, uint32_t r, const u
     if (flags) flags[r] = hu ? WEPP_FLAG_HAS_UNIQUE_DEV : 0u;
 }
 
+// -----------------------------------------------------------------------------
+// A read with MANY events at its positions: lane = list entry, no walk (the method: wave_kernels.hip).  The device code
+// lives here because two units run it: k_walk_wave (wave_kernels.hip) and the wave-role workgroups of k_step
+// (walk_kernels.hip), which are compiled separately.
+// -----------------------------------------------------------------------------
+constexpr uint32_t WW_R = WAVE_WALK_MAX_EVENTS / 64;      // rows of 64 entries of the largest read: entries per lane
+constexpr int PK_BIAS = 2;
+// LDS of a block of `waves` waves (words): the per-entry partials of the pair pass, one unit = (row of 64 entries, slice of
+// the broadcasts), five words a lane; behind them four words per wave for the block's combination of its waves' bests
+constexpr uint32_t WW_UNITS_MAX = 6, WW_UNIT_WORDS = 5 * 64;
+__host__ __device__ constexpr uint32_t ww_lds_words(uint32_t waves) { return WW_UNITS_MAX * WW_UNIT_WORDS + 4 * waves; }
+
+struct Cand {
+    int bs;
+    uint32_t br, cnt, hu;
+};
+__device__ __forceinline__ void cand_take(Cand& c, int sc, uint32_t rk, uint32_t kk, uint32_t hu) {
+    if (sc < c.bs) { c.bs = sc; c.br = rk; c.cnt = kk; c.hu = hu; }
+    else if (sc == c.bs) { c.cnt += kk; if (rk < c.br) { c.br = rk; c.hu = hu; } }
+}
+
+// best statically eligible node of the untouched nodes [pos, stop) of an arena slice whose running c_S is `c`: the
+// sparse table's byte says whether anything there can reach the bound, then the exact aggregate (as in k_walk)
+__device__ __forceinline__ void range_candidate(const DevWalk& ix, const WcInfo& wi, uint32_t pos, uint32_t stop, int c, Cand& best, uint32_t& bytes) {
+    const uint32_t len = stop - pos;
+    const uint32_t lvl = len > 1 ? 32u - (uint32_t)__builtin_clz(len - 1) : 0u;
+    const uint32_t mn = ix.sp[(size_t)wi.sp_off + (size_t)lvl * wi.n + pos];
+    bytes += 1;
+    if (mn == SP_NONE || (mn < SP_CLAMP && (int)mn + c > best.bs)) return;
+    const uint32_t last = stop - 1, ba = pos / RQ_BLK, bl = last / RQ_BLK;
+    SegNode ag{SCORE_INF_DEV, 0xFFFFFFFFu, 0u, 0u};
+    auto join = [&](const SegNode x) {
+        if (x.base < ag.base) ag = x;
+        else if (x.base == ag.base) { ag.cnt += x.cnt; if (x.rank < ag.rank) { ag.rank = x.rank; ag.hu = x.hu; } }
+    };
+    if (ba == bl) {
+        bytes += 16;
+        if (pos == ba * RQ_BLK) join(ix.rq_pre[wi.node_off + last]);
+        else if (stop == wi.n || stop == (ba + 1) * RQ_BLK) join(ix.rq_suf[wi.node_off + pos]);
+        else
+            for (uint32_t i = pos; i < stop; i++) {
+                const NodeRec x = ix.nrec[wi.node_off + i];
+                if (x.nstat & NS_ELIG0_DEV) {
+                    const uint32_t hu = (x.nstat & NS_ROOT_DEV) ? 0u : (x.nstat & NS_MASKED_DEV) ? 1u :
+                                        (((x.nstat >> 14) & NS_CNT_MASK_DEV) < (x.nstat & NS_CNT_MASK_DEV) ? 1u : 0u);
+                    join(SegNode{x.base, x.rank, 1u, hu});
+                }
+            }
+    } else {
+        const uint32_t lo = ba + 1, hi = bl - 1;
+        const SegNode none{SCORE_INF_DEV, 0xFFFFFFFFu, 0u, 0u};
+        const uint32_t L = lo < hi ? 31u - (uint32_t)__builtin_clz(lo ^ hi) : 0u;
+        const SegNode* trow = ix.rq_dst + wi.dst_off + (size_t)L * wi.rq_blocks;
+        const SegNode s1 = ix.rq_suf[wi.node_off + pos], s2 = ix.rq_pre[wi.node_off + last];
+        const SegNode s3 = lo <= hi ? trow[lo] : none, s4 = lo < hi ? trow[hi] : none;
+        join(s1); join(s2); join(s3); join(s4);
+        bytes += 64;
+    }
+    if (ag.cnt && ag.base + c <= best.bs) cand_take(best, ag.base + c, ag.rank, ag.cnt, ag.hu);
+}
+
+// the lists of one read, as every wave that works on it sees them: lane j < k holds list j
+struct ReadLists {
+    uint32_t k, E, w, off, len, start;
+    int c0;
+};
+__device__ __forceinline__ ReadLists read_lists(const DevMAT& m, const DevWalk& ix, const WcInfo& wi, uint32_t lane, uint32_t rd,
+                                                const uint32_t* __restrict__ read_off, const uint32_t* __restrict__ read_word) {
+    ReadLists L;
+    const uint32_t so = read_off[rd];
+    L.k = read_off[rd + 1] - so;                         // (k <= WALK16_K: k_route)
+    L.w = lane < L.k ? read_word[so + lane] : 0u;
+    L.off = L.len = 0;
+    if (lane < L.k && w_pos(L.w) <= m.max_pos) {
+        const uint32_t o0 = ix.ix_head[wi.head_off + w_pos(L.w)].off, o1 = ix.ix_head[wi.head_off + w_pos(L.w) + 1].off;
+        L.off = o0;
+        L.len = o1 - o0 - 1u;                            // (every list ends in a sentinel)
+    }
+    const uint32_t incl = wave_scan_add_u32(L.len);
+    L.start = incl - L.len;
+    L.E = min((uint32_t)__builtin_amdgcn_readlane((int)incl, 63), WAVE_WALK_MAX_EVENTS);   // (k_route admits no more)
+    L.c0 = (int)__popcll(__ballot(lane < L.k && !rw_missing(L.w) && (rw_mut(L.w) & rw_ref(L.w)) == 0));
+    return L;
+}
+// entry i of the concatenated lists: its place in the index and the read's word for its position
+__device__ __forceinline__ void locate(const ReadLists& L, uint32_t i, uint32_t& e, uint32_t& sw) {
+    e = NONE; sw = 0;
+    for (uint32_t j = 0; j < L.k; j++) {
+        const uint32_t sj = (uint32_t)__builtin_amdgcn_readlane((int)L.start, (int)j), lj = (uint32_t)__builtin_amdgcn_readlane((int)L.len, (int)j);
+        const uint32_t oj = (uint32_t)__builtin_amdgcn_readlane((int)L.off, (int)j), wj = (uint32_t)__builtin_amdgcn_readlane((int)L.w, (int)j);
+        if (i - sj < lj) { e = oj + (i - sj); sw = wj; }
+    }
+}
+// the three adjustments of an entry (the delta -2 .. 2, the other two -1 .. 1), each biased by PK_BIAS in a byte of its
+// own, and a one in the top byte: the sum over the <= 16 entries of one node (one per listed position) stays inside
+__device__ __forceinline__ uint32_t pack_adjust(const IxEnt& ent, uint32_t sw) {
+    int d = 0, adj = 0, dcom = 0;
+    // descendants take the allele; the root also scores itself with it (usher_mapper.cpp:266-271)
+    if (ent.end > ent.node + 1 || ent.node == 0) d = enter_delta(ent.word, sw);
+    own_adjust(ent.word, sw, adj, dcom);
+    return (uint32_t)(d + PK_BIAS) | (uint32_t)(adj + PK_BIAS) << 8 | (uint32_t)(dcom + PK_BIAS) << 16 | 1u << 24;
+}
+
+// What the pair pass accumulates for one entry.  Every field is associative and commutative -- cb, cB and T are sums,
+// stopA and stopB minima, fl an OR -- so the broadcasts of a read may be cut into slices that different waves take, and
+// the partials joined in any order: the result is the same, bit for bit.
+struct PairAcc {
+    int cb, cB;
+    uint32_t T, stopA, stopB, fl;      // fl bit 0: an entry of the same node with a lower index; bit 1: ... of the same subtree end
+};
+__device__ __forceinline__ void pair_join(PairAcc& a, const PairAcc& b) {
+    a.cb += b.cb; a.cB += b.cB; a.T += b.T;
+    a.stopA = min(a.stopA, b.stopA); a.stopB = min(a.stopB, b.stopB);
+    a.fl |= b.fl;
+}
+
+// The work of ONE wave of a workgroup of W waves on one read of E <= 64 R entries.  The wave holds all entries for the
+// broadcasts (lane + 64 r).  The pair pass is cut into units = (row of 64 entries, slice of the broadcasts): a read of
+// `rows` rows takes P slices so that every wave of the workgroup has pairs to score -- the pass is the time of such a
+// read, ~20 instructions a pair on a single wave --, wave u % W takes unit u, and the partials of a row meet in LDS
+// (`part`, ww_lds_words) where wave row % W joins them, scores the row's nodes and asks for their stretches.
+template <uint32_t R, uint32_t W>
+__device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, uint32_t lane, uint32_t wv, const ReadLists& L, uint32_t* part, Cand& best,
+                                          uint32_t& bytes, uint32_t& wave_bytes) {
+    constexpr uint32_t OWN = (R + W - 1) / W;      // rows a wave finishes
+    const uint32_t E = L.E;
+    const int c0 = L.c0;
+    uint32_t bnode[R], bend[R], bpk[R];
+    uint32_t orank[OWN], onst[OWN];
+    int obase[OWN];
+#pragma unroll
+    for (uint32_t r = 0; r < R; r++) {
+        const uint32_t i = lane + 64 * r;
+        bnode[r] = bend[r] = NONE; bpk[r] = 0;
+        if (r % W == 0) { orank[r / W] = 0; onst[r / W] = 0; obase[r / W] = 0; }
+        uint32_t e, sw;
+        locate(L, i, e, sw);
+        if (i < E && e != NONE) {
+            const IxEnt ent = ix.ix_ent[e];
+            bnode[r] = ent.node;
+            bend[r] = ent.end;
+            bpk[r] = pack_adjust(ent, sw);
+            if (r % W == wv) {
+                obase[r / W] = ent.base;
+                orank[r / W] = wi.has_pre ? ent.rank & IX_RANK_MASK : ent.rank;
+                onst[r / W] = ent.nstat;
+            }
+        }
+    }
+    const uint32_t rows = max((E + 63) / 64, 1u);
+    const uint32_t P = R == 1 ? 1u : W >= 2 * rows ? W / rows : (rows % W ? 2u : 1u);
+    const uint32_t H = (E + P - 1) / P;            // broadcasts of a slice
+    // ---- all pairs: what a sequential walk would know at every entry.  Subtrees nest, so for entry (n, e):
+    //   cb  = the deltas of the entries whose subtree holds n strictly inside (nl < n < el);
+    //   T   = the packed sum over the entries of the same node (the lowest of them owns the node and its stretches);
+    //   the stretch of untouched descendants starts at n + 1 with c_S = cb + the node's own deltas and stops at the first
+    //   entry node or subtree end at or behind n + 1 (its own end at the latest: a leaf's stretch is empty);
+    //   the stretch behind the subtree starts at e with cB = the deltas of the subtrees that hold e strictly inside and
+    //   stops at the first entry node at or behind e, or subtree end behind e; of the entries that end at e the lowest
+    //   owns it.  Differences wrap to huge values when the cut lies in front of the start, so plain minima do.
+    //   "Lower" compares the entries' indices in the read, whatever slice a broadcast comes from.
+    auto pass = [&](uint32_t row, uint32_t s0, uint32_t s1) -> PairAcc {
+        uint32_t node = NONE, end = NONE;
+#pragma unroll
+        for (uint32_t r = 0; r < R; r++) if (r == row) { node = bnode[r]; end = bend[r]; }
+        PairAcc a{0, 0, 0u, NONE, NONE, 0u};
+        unsigned long long lower_same = 0ull, lower_end = 0ull;
+        const uint32_t mg = row * 64 + lane, sA = node + 1u, e2 = end << 1;
+#pragma unroll
+        for (uint32_t rl = 0; rl < R; rl++) {
+            const uint32_t lo = s0 > 64 * rl ? s0 - 64 * rl : 0u, hi = s1 > 64 * rl ? min(64u, s1 - 64 * rl) : 0u;
+            for (uint32_t ll = lo; ll < hi; ll++) {
+                const uint32_t nl = (uint32_t)__builtin_amdgcn_readlane((int)bnode[rl], (int)ll), el = (uint32_t)__builtin_amdgcn_readlane((int)bend[rl], (int)ll);
+                const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)bpk[rl], (int)ll);
+                const int dl = (int)(pl & 0xFFu) - PK_BIAS;
+                const uint32_t g = rl * 64 + ll, nl1 = nl + 1u, span = el - nl1, nl2 = nl << 1, el2 = (el << 1) - 1u;
+                const unsigned long long lower = __ballot(g < mg);
+                if (dl != 0) {
+                    if (node - nl1 < span) a.cb += dl;
+                    if (end - nl1 < span) a.cB += dl;
+                }
+                const bool same = nl == node;
+                a.T += same ? pl : 0u;
+                lower_same |= __ballot(same) & lower;
+                lower_end |= __ballot(el == end) & lower;
+                a.stopA = min(a.stopA, min(nl - sA, el - sA));
+                a.stopB = min(a.stopB, min(nl2 - e2, el2 - e2));       // (entry nodes at e cut, ends behind e cut)
+            }
+        }
+        a.fl = (uint32_t)((lower_same >> lane) & 1ull) | (uint32_t)((lower_end >> lane) & 1ull) << 1;
+        return a;
+    };
+    // ---- every lane: its node, its stretches ----
+    auto finish = [&](uint32_t row, const PairAcc& a, int base, uint32_t rank, uint32_t nst) {
+        uint32_t node = NONE, end = NONE;
+#pragma unroll
+        for (uint32_t r = 0; r < R; r++) if (r == row) { node = bnode[r]; end = bend[r]; }
+        if (node != NONE) {
+            const uint32_t sA = node + 1u;
+            const uint32_t cnt = PK_BIAS * (a.T >> 24);
+            const int dsumT = (int)(a.T & 0xFFu) - (int)cnt, adjT = (int)((a.T >> 8) & 0xFFu) - (int)cnt, dcomT = (int)((a.T >> 16) & 0xFFu) - (int)cnt;
+            if (!(a.fl & 1u)) {
+                const uint32_t nmut = nst & NS_CNT_MASK_DEV, ncom0 = (nst >> 14) & NS_CNT_MASK_DEV;
+                const bool leaf = nst & NS_LEAF_DEV, masked = nst & NS_MASKED_DEV, root = nst & NS_ROOT_DEV;
+                const int c = c0 + a.cb;
+                if (root) { if (base + c + dsumT <= best.bs) cand_take(best, base + c + dsumT, rank, 1u, 0u); }
+                else if (!masked) {
+                    const int sc = base + c + adjT, ncom = (int)ncom0 + dcomT;
+                    const bool elig = leaf ? (ncom > 0) : (ncom > 0 || ncom == (int)nmut);     // usher_mapper.cpp:455-456
+                    if (elig && sc <= best.bs) cand_take(best, sc, rank, 1u, ncom < (int)nmut ? 1u : 0u);
+                }
+                const uint32_t eA = min(sA + a.stopA, wi.n);
+                if (sA < eA) range_candidate(ix, wi, sA, eA, c0 + a.cb + dsumT, best, bytes);
+            }
+            if (!(a.fl & 2u)) {
+                const uint32_t eB = a.stopB >= 0x80000000u ? wi.n : min(end + ((a.stopB + 1u) >> 1), wi.n);     // (no cut behind e: the keys are below 2 n)
+                if (end < eB) range_candidate(ix, wi, end, eB, c0 + a.cB, best, bytes);
+            }
+        }
+        if (row == 0) {
+            // the stretch from node 0 on is nobody's: the first lane asks for it
+            uint32_t first_node = bnode[0];
+#pragma unroll
+            for (uint32_t r = 1; r < R; r++) first_node = min(first_node, bnode[r]);
+            first_node = wave_min_u32(first_node);
+            if (lane == 0 && first_node != 0u && wi.n > 0) range_candidate(ix, wi, 0u, min(first_node, wi.n), c0, best, bytes);
+        }
+        // (the read's offsets, words, list heads and stream record once; a 32-byte index entry per list entry)
+        wave_bytes += (row == 0 ? 8 + 12 * L.k + 80 + 16 : 0) + 32 * min(64u, E - 64 * row);
+    };
+    if (R == 1) {
+        finish(0u, pass(0u, 0u, E), obase[0], orank[0], onst[0]);
+        return;
+    }
+    for (uint32_t u = wv; u < rows * P; u += W) {
+        const uint32_t row = u / P, p = u - row * P;
+        const PairAcc a = pass(row, p * H, min(E, (p + 1) * H));
+        uint32_t* o = part + u * WW_UNIT_WORDS + lane;
+        // (|cb|, |cB| <= 2 * 256: sixteen bits each)
+        o[0] = ((uint32_t)a.cb & 0xFFFFu) | (uint32_t)a.cB << 16; o[64] = a.T; o[128] = a.stopA; o[192] = a.stopB; o[256] = a.fl;
+    }
+    __syncthreads();
+#pragma unroll
+    for (uint32_t j = 0; j < OWN; j++) {
+        const uint32_t row = wv + j * W;
+        if (row >= rows) break;
+        PairAcc a{0, 0, 0u, NONE, NONE, 0u};
+        for (uint32_t p = 0; p < P; p++) {
+            const uint32_t* o = part + (row * P + p) * WW_UNIT_WORDS + lane;
+            const uint32_t cc = o[0];
+            pair_join(a, PairAcc{(int)(int16_t)(cc & 0xFFFFu), (int)cc >> 16, o[64], o[128], o[192], o[256]});
+        }
+        finish(row, a, obase[j], orank[j], onst[j]);
+    }
+}
+
+// The many-event reads of a call, by the waves of workgroup `blk` of `n_blk` workgroups of W waves that loop over the list:
+// list[0 .. count[0]): reads with <= 64 events, a wave each; list[n_reads - count[1] .. n_reads), from the back: reads
+// with more, all waves of a workgroup each, first.  `lds`: ww_lds_words(W) words.
+template <uint32_t W>
+__device__ __forceinline__ void wave_walk_body(const DevMAT& m, uint32_t* lds, uint32_t blk, uint32_t n_blk, const uint32_t* __restrict__ list,
+                                               uint32_t n_small, uint32_t n_big, uint32_t n_reads,
+                                               const uint32_t* __restrict__ read_off, const uint32_t* __restrict__ read_word,
+                                               const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
+                                               int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                               uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
+                                               const uint32_t* __restrict__ wsid) {
+    static_assert(W == 2 || W == 4, "the slices of wave_read are laid out for two or four waves");
+    static_assert(WW_R == 4 && WW_UNITS_MAX == 6, "the largest read has four rows: at most six units (three rows, two slices)");
+    uint32_t* part_w = lds + WW_UNITS_MAX * WW_UNIT_WORDS;      // [4][W]: score, total, rank, has_unique of every wave
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const DevWalk ix = m.walks[WC_SLOT];                 // the walk arena: every stream is a slice of it
+    uint32_t bytes = 0, wave_bytes = 0;     // what the lanes / the wave as a whole asked memory for
+    auto reduce = [&](const Cand& best, int& smin, uint32_t& total, uint32_t& rmin, bool& hu) {
+        smin = wave_min_i32(best.cnt ? best.bs : 0x7FFFFFFF);
+        const bool at = best.cnt && best.bs == smin;
+        total = wave_sum_u32(at ? best.cnt : 0u);
+        rmin = wave_min_u32(at ? best.br : 0xFFFFFFFFu);
+        hu = __ballot(at && best.br == rmin && best.hu) != 0ull;
+    };
+    auto emit = [&](uint32_t rd, int smin, uint32_t total, uint32_t rmin, bool hu) {
+        if (best_bfs_j) best_bfs_j[rd] = m.rank2bfs[rmin < m.N ? rmin : 0u];
+        if (score_out) score_out[rd] = smin;
+        if (num_best) num_best[rd] = total;
+        if (flags) flags[rd] = hu ? WEPP_FLAG_HAS_UNIQUE_DEV : 0u;
+    };
+    for (uint32_t it = blk; it < n_big; it += n_blk) {
+        const uint32_t rd = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[n_reads - 1u - it]);
+        const WcInfo wi = m.wc_info[wsid[rd]];
+        const ReadLists L = read_lists(m, ix, wi, lane, rd, read_off, read_word);
+        Cand best{root_score[rd] + 1, 0xFFFFFFFFu, 0u, 0u};        // the root always competes: nothing worse can win or tie
+        if (L.E <= 128) wave_read<2, W>(ix, wi, lane, wv, L, lds, best, bytes, wave_bytes);
+        else wave_read<WW_R, W>(ix, wi, lane, wv, L, lds, best, bytes, wave_bytes);
+        int smin; uint32_t total, rmin; bool hu;
+        reduce(best, smin, total, rmin, hu);
+        if (lane == 0) { part_w[wv] = (uint32_t)smin; part_w[W + wv] = total; part_w[2 * W + wv] = rmin; part_w[3 * W + wv] = hu ? 1u : 0u; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (uint32_t v = 1; v < W; v++) {
+                const int sv = (int)part_w[v];
+                const uint32_t tv = part_w[W + v], rv = part_w[2 * W + v];
+                if (sv < smin) { smin = sv; total = tv; rmin = rv; hu = part_w[3 * W + v]; }
+                else if (sv == smin && tv) { total += tv; if (rv < rmin) { rmin = rv; hu = part_w[3 * W + v]; } }
+            }
+            emit(rd, smin, total, rmin, hu);
+        }
+        __syncthreads();
+    }
+    // (the small reads are dealt from the END of the grid: the first workgroups hold the large ones)
+    for (uint32_t it = n_blk * W - 1u - (blk * W + wv); it < n_small; it += n_blk * W) {
+        const uint32_t rd = (uint32_t)__builtin_amdgcn_readfirstlane((int)list[it]);
+        const WcInfo wi = m.wc_info[wsid[rd]];
+        const ReadLists L = read_lists(m, ix, wi, lane, rd, read_off, read_word);
+        Cand best{root_score[rd] + 1, 0xFFFFFFFFu, 0u, 0u};
+        wave_read<1, W>(ix, wi, lane, 0u, L, lds, best, bytes, wave_bytes);
+        int smin; uint32_t total, rmin; bool hu;
+        reduce(best, smin, total, rmin, hu);
+        if (lane == 0) emit(rd, smin, total, rmin, hu);
+    }
+    wave_bytes += wave_sum_u32(bytes);
+    if (work_counter && lane == 0 && wave_bytes)
+        atomicAdd(work_counter + WALK_COUNTERS + ((blk * W + wv) & (WALK_COUNTERS - 1)), (unsigned long long)wave_bytes);
+}
+
 }  // namespace
 
 }  // namespace wepp

@@ -25,20 +25,21 @@ namespace wepp {
 // 2 events instead of 270 blocks on the 17 K-node crown, ~3.5 K instead of 250 K blocks on the
 // whole tree for a read with three entries.  Same results (tests/walk_model.py is the CPU model).
 // -----------------------------------------------------------------------------
+// (the body of k_walk as a device function: k_step below runs it in its walker workgroups too.  `wg` = the workgroup's
+// index among the walkers of the launch, `lds_all` = the workgroup's dynamic LDS)
 template <int KW, int SD, bool CHUNKED>
-__global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl, WalkJobs jb, uint32_t sd_rows,
-                                              const uint32_t* __restrict__ read_off,
-                                              const uint32_t* __restrict__ read_word,
-                                              const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
-                                              int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
-                                              uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
-                                              const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ blind_list,
-                                              const uint32_t* __restrict__ blind_count) {
+__device__ __forceinline__ void walk_body(const DevMAT& m, const WalkPlans& pl, const WalkJobs& jb, uint32_t sd_rows, uint32_t wg, uint32_t* lds_all,
+                                          const uint32_t* __restrict__ read_off,
+                                          const uint32_t* __restrict__ read_word,
+                                          const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
+                                          int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                          uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
+                                          const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ blind_list,
+                                          const uint32_t* __restrict__ blind_count) {
     // wave-private LDS: the allele fields of the read words, 16 bits each [KW / 2][64]; the list cursors [KW][64];
     // the interval stack [sd_rows][64] -- sd_rows = the deepest stack a read of this launch can need (k_route's
     // maximum of open_max over the class, <= SD).  The walk waits on memory: what it gains from a wave more
     // per SIMD is nearly proportional, and its LDS request is what limits them.
-    extern __shared__ uint32_t lds_all[];
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint32_t* S16 = lds_all + wv * (KW / 2 + KW + sd_rows) * 64;
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl
     uint32_t* stk = cur_l + KW * 64;
     // the read word of list j rebuilt from its 9 allele bits (the position is not needed again)
     auto sword = [&](int j) -> uint32_t { return ((S16[(j >> 1) * 64 + lane] >> ((j & 1) * 16)) & 0x1FFu) << 20; };
-    const uint32_t unit = blockIdx.x * WALK_WAVES + wv;
+    const uint32_t unit = wg * WALK_WAVES + wv;
     // BLIND (plain walks of a placement call): the launch was sized for the worst case before the routing counters
     // reached the host; the reads are k_route's list blind_list[0 .. *blind_count) and every read walks the arena slice
     // wsid names.  Waves beyond the count leave at once.
@@ -509,6 +510,61 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl
 #endif
 }
 
+template <int KW, int SD, bool CHUNKED>
+__global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl, WalkJobs jb, uint32_t sd_rows,
+                                              const uint32_t* __restrict__ read_off,
+                                              const uint32_t* __restrict__ read_word,
+                                              const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
+                                              int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                              uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
+                                              const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ blind_list,
+                                              const uint32_t* __restrict__ blind_count) {
+    extern __shared__ uint32_t lds_all[];
+    walk_body<KW, SD, CHUNKED>(m, pl, jb, sd_rows, blockIdx.x, lds_all, read_off, read_word, root_score, best_bfs_j, score_out, num_best, flags,
+                               work_counter, wsid, blind_list, blind_count);
+}
+
+// -----------------------------------------------------------------------------
+// k_step: the two common classes of a placement call in ONE launch on the caller's stream, right behind k_route -- the
+// plain walkers of up to WALK8_K entries (k_route's list wlist, lane = read) and the reads with many events (its two-ended
+// list wwlist, lane = list entry: place_dev.hpp wave_walk_body).  A workgroup takes its role from the counters k_route
+// has left on the device: the first n_wave workgroups -- dispatched first, so the longest items of the step, the reads
+// with more than 64 events, start first -- work on wwlist, every later one is a walker numbered from zero.  n_wave is
+// what the counters ask for (a workgroup per read with more than 64 events, a wave per smaller one), rounded up to a
+// multiple of WALK_XCDS so that a walker's XCD is still its own index % 8, at most `wave_cap` (beyond, the wave-role
+// workgroups loop); with wave_cap = 0 (the handle cuts such reads into jobs: the lists are empty) this is the blind
+// k_walk<WALK8_K>.  Both roles live in the walkers' dynamic LDS: the launch asks for what k_walk asks.
+// -----------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * WALK_WAVES) void k_step(DevMAT m, uint32_t sd_rows, uint32_t wave_cap, uint32_t n_reads,
+                                              const uint32_t* __restrict__ read_off,
+                                              const uint32_t* __restrict__ read_word,
+                                              const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
+                                              int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                              uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
+                                              const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ wlist,
+                                              const uint32_t* __restrict__ wcount, const uint32_t* __restrict__ wwlist,
+                                              const uint32_t* __restrict__ wwcount) {
+    extern __shared__ uint32_t lds_all[];
+    uint32_t n_wave = 0, n_small = 0, n_big = 0;
+    if (wave_cap) {
+        n_small = (uint32_t)__builtin_amdgcn_readfirstlane((int)wwcount[0]);
+        n_big = (uint32_t)__builtin_amdgcn_readfirstlane((int)wwcount[1]);
+        // (both counts are at most n_reads: no overflow)
+        const uint32_t want = n_big + (n_small + WALK_WAVES - 1) / WALK_WAVES;
+        n_wave = min((want + WALK_XCDS - 1) / WALK_XCDS * WALK_XCDS, wave_cap);
+    }
+    if (blockIdx.x < n_wave) {
+        wave_walk_body<WALK_WAVES>(m, lds_all, blockIdx.x, n_wave, wwlist, n_small, n_big, n_reads, read_off, read_word, root_score, best_bfs_j, score_out,
+                                   num_best, flags, work_counter, wsid);
+    } else {
+        WalkPlans pl{};
+        pl.n = 1;
+        const WalkJobs none{};
+        walk_body<(int)WALK8_K, (int)WALK8_STACK, false>(m, pl, none, sd_rows, blockIdx.x - n_wave, lds_all, read_off, read_word, root_score, best_bfs_j,
+                                                         score_out, num_best, flags, work_counter, wsid, wlist, wcount);
+    }
+}
+
 // job counts in list order (the input of the scan)
 __global__ void k_gather_jobs(const uint32_t* __restrict__ list, uint32_t n_list, const uint32_t* __restrict__ job_n,
                               uint32_t* __restrict__ out) {
@@ -633,6 +689,21 @@ hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows,
         hipLaunchKernelGGL((k_walk<(int)WALK16_K, (int)WALK16_STACK, false>), grid, block, walk_lds_bytes(WALK16_K, sd), stream, m, pl,
                            none, sd, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, list, count);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_step(const DevMAT& m, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
+                       const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
+                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
+    static_assert(STEP_WAVE_WGS % WALK_XCDS == 0, "the walkers behind the wave-role workgroups keep their XCD order");
+    if (max_reads == 0) return hipSuccess;
+    const uint32_t wave_cap = wwlist ? STEP_WAVE_WGS : 0u;
+    const uint32_t sd = walk_stack_rows(stack_rows, WALK8_STACK);
+    // (with the default stack rows the walkers' request is the larger one)
+    const uint32_t lds = std::max(walk_lds_bytes(WALK8_K, sd), wave_cap ? ww_lds_words(WALK_WAVES) * 4u : 0u);
+    const dim3 grid(wave_cap + walk_plan_waves(max_reads) / WALK_WAVES), block(64 * WALK_WAVES);
+    hipLaunchKernelGGL(k_step, grid, block, lds, stream, m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags,
+                       work_counter, wsid, wlist, wcount, wwlist, wwcount);
     return hipGetLastError();
 }
 
