@@ -470,6 +470,53 @@ int wepp_mat_dfs_order(const wepp_mat_t *mat, uint32_t *ids);
 int wepp_epp_last_timing(double *select_ms, double *sweep1_ms, double *sweep2_ms, double *finish_ms,
                          uint64_t *events_swept, uint64_t *stream_events, uint32_t *groups, uint32_t *jobs);
 
+/* ---- reads against a selection of haplotypes ------------------------------- *
+ * Replaces the loop of arena::dump_read2haplotype_mapping (src/WEPP/arena.cpp:610-667;
+ * the same loop in arena::resolve_unaccounted_mutations, :833-866): every read against
+ * every SELECTED haplotype through haplotype::mutation_distance (src/WEPP/haplotype.hpp:
+ * 123-177).  How the selection was made (peak loop, Freyja, a list the user brings) is the
+ * caller's business.  `mat` is the handle of the condensed tree, `reads` a batch as for
+ * wepp_epp_map, sel[0 .. n_sel) distinct arena (pre-order) indices in the caller's order
+ * (the reference's `abundance` order).  d(r, k) = the distance of read r to haplotype
+ * sel[k], whose stack_muts are as arena::from_mat builds them (arena.cpp:17-48): the
+ * deepest mutation of the root path wins at a position and is kept when mut_nuc != ref_nuc.
+ * Outputs (all host buffers):
+ *   min_dist[R]      min over k of d(r, k)                        (arena.cpp:614-625)
+ *   n_epp[R]         number of k attaining it
+ *   asg_off/asg_sel  the reference's `epps` per read: the indices INTO sel attaining the
+ *                    minimum, ascending, as a CSR over the reads (asg_off[R + 1]); both or
+ *                    neither -- asg_off alone with asg_capacity = 0 asks for the sizes only
+ *   sel_reads[K]     reads whose set holds k
+ *   sel_degree[K]    sum of their degree                          (the count of :859-865)
+ *   sel_covered[K]   sites j, 1 <= j <= genome_size, inside [start, end] of at least one
+ *                    read assigned to k at which that read lists no N (:637-665); the
+ *                    coverage file holds sel_covered / genome_size (:681-688)
+ *   cover_bits       the coverage bitmaps themselves, K rows of ceil(genome_size / 32)
+ *                    words, bit (j - 1) & 31 of word (j - 1) / 32 for site j; may be NULL.
+ *                    Shards of a read set are combined by OR (sel_reads / sel_degree by +).
+ * Everything is integer and independent of the order of execution: bit-identical run to run.
+ * Preconditions on the reads: those of wepp_epp_map, same codes and messages; genome_size
+ * >= 1 (the 50-bin rule belongs to the map).  WEPP_EINVAL: n_sel == 0, an index >= n_nodes,
+ * a repeated index.  WEPP_ELIMIT: the device table of the selection (3 bytes per tree
+ * position and haplotype, columns padded to 256) would exceed 1 GiB -- assign to the
+ * selection in parts --; a selected haplotype with more than 65535 non-reference positions
+ * (16-bit prefix counts); asg_capacity < asg_off[n_reads] -- then EVERY other output is
+ * delivered, asg_off is filled, and the caller calls again with a buffer of asg_off[n_reads]
+ * entries: nothing is kept pending on the handle, a second call is cheap here, unlike the map.
+ * n_reads == 0: the per-haplotype outputs are zero, asg_off[0] = 0.  Serial per handle, like
+ * wepp_epp_map, whose device block cache it shares. */
+typedef struct {
+    int32_t *min_dist; uint32_t *n_epp;          /* [n_reads] */
+    uint64_t *asg_off; uint32_t *asg_sel; uint64_t asg_capacity;   /* both or neither */
+    uint32_t *sel_reads; int64_t *sel_degree; uint32_t *sel_covered;   /* [n_sel] */
+    uint32_t *cover_bits;                         /* [n_sel * ceil(genome_size/32)] or NULL */
+} wepp_assign_out;
+int wepp_epp_assign(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t genome_size,
+                    uint32_t n_sel, const uint32_t *sel, wepp_assign_out *out);
+/* device time of the calling thread's last wepp_epp_assign by phase (HIP events, ms): the selection's
+ * genotype table, reads x selection (k_assign), lists + coverage counts */
+int wepp_epp_assign_last_timing(double *tables_ms, double *assign_ms, double *finish_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

@@ -127,6 +127,12 @@ class EppOutC(ctypes.Structure):
                 ("hap_read_counts", ctypes.c_void_p), ("hap_divergence", ctypes.c_void_p)]
 
 
+class AssignOutC(ctypes.Structure):
+    _fields_ = [("min_dist", ctypes.c_void_p), ("n_epp", ctypes.c_void_p), ("asg_off", ctypes.c_void_p),
+                ("asg_sel", ctypes.c_void_p), ("asg_capacity", ctypes.c_uint64), ("sel_reads", ctypes.c_void_p),
+                ("sel_degree", ctypes.c_void_p), ("sel_covered", ctypes.c_void_p), ("cover_bits", ctypes.c_void_p)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -176,6 +182,9 @@ _SIGS = {
     "wepp_epp_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4 + [
         ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint32),
         ctypes.POINTER(ctypes.c_uint32)]),
+    "wepp_epp_assign": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.c_uint32, _V,
+                                       ctypes.POINTER(AssignOutC)]),
+    "wepp_epp_assign_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

@@ -516,6 +516,46 @@ class Mat:
             out["epp_nodes"] = enodes[: int(eoff[R])]
         return out
 
+    def epp_assign(self, reads, genome_size, sel, want_lists=True, want_bits=False, asg_capacity=None):
+        """wepp_epp_assign: every read of an EppReads batch against the selected haplotypes sel (distinct arena
+        indices, the caller's order).  Returns min_dist / n_epp per read, asg_off / asg_sel (CSR of the indices INTO
+        sel attaining the minimum, ascending), sel_reads / sel_degree / sel_covered per selected haplotype and, with
+        want_bits, cover_bits [len(sel), ceil(genome_size / 32)]."""
+        R = reads.n_reads
+        sel = np.ascontiguousarray(sel, dtype=np.uint32)
+        K = int(sel.size)
+        md = np.zeros(max(R, 1), np.int32); ne = np.zeros(max(R, 1), np.uint32)
+        sr = np.zeros(max(K, 1), np.uint32); sd = np.zeros(max(K, 1), np.int64); sc = np.zeros(max(K, 1), np.uint32)
+        bits = np.zeros((K, (int(genome_size) + 31) // 32), np.uint32) if want_bits else None
+        # a guess: most reads tie on a handful of the selected haplotypes
+        cap = int(asg_capacity if asg_capacity is not None else 8 * max(R, 1))
+        aoff = np.zeros(R + 1, np.uint64) if want_lists else None
+        asel = np.zeros(max(cap, 1), np.uint32) if want_lists else None
+        rw = reads.read_word if reads.read_word.size else np.zeros(1, np.uint32)
+        rd = _lib.EppReadsC(R, _ptr(reads.read_off).value, _ptr(rw).value, _ptr(reads.start).value,
+                            _ptr(reads.end).value, _ptr(reads.degree).value)
+
+        def call():
+            o = _lib.AssignOutC(_ptr(md).value, _ptr(ne).value, _ptr(aoff).value if want_lists else None,
+                                _ptr(asel).value if want_lists else None, cap, _ptr(sr).value, _ptr(sd).value,
+                                _ptr(sc).value, _ptr(bits).value if want_bits and bits.size else None)
+            return lib.wepp_epp_assign(self._h, ctypes.byref(rd), int(genome_size), K, _ptr(sel) if K else None,
+                                       ctypes.byref(o))
+        rc = call()
+        if rc == 4 and want_lists and int(aoff[R]) > cap:
+            # the guess was short: asg_off[R] is the size, and a second call is cheap
+            cap = int(aoff[R])
+            asel = np.zeros(cap, np.uint32)
+            rc = call()
+        check(rc)
+        out = dict(min_dist=md[:R], n_epp=ne[:R], sel_reads=sr[:K], sel_degree=sd[:K], sel_covered=sc[:K])
+        if want_lists:
+            out["asg_off"] = aoff
+            out["asg_sel"] = asel[: int(aoff[R])]
+        if want_bits:
+            out["cover_bits"] = bits
+        return out
+
     def imputed_mutations(self, reads, best_bfs_j):
         """Per read: list of (position, nucleotide mask) imputed for its ambiguous entries at
         the chosen node (column 4 of placement_stats.tsv): wepp_imputed_mutations."""
@@ -599,3 +639,10 @@ def epp_last_timing():
                                    ctypes.byref(j)))
     return dict(select_ms=d[0].value, sweep1_ms=d[1].value, sweep2_ms=d[2].value, finish_ms=d[3].value,
                 events_swept=ev.value, stream_events=se.value, groups=g.value, jobs=j.value)
+
+
+def epp_assign_last_timing():
+    """Device time by phase (ms) of this thread's last Mat.epp_assign call."""
+    d = [ctypes.c_double() for _ in range(3)]
+    check(lib.wepp_epp_assign_last_timing(*[ctypes.byref(x) for x in d]))
+    return dict(tables_ms=d[0].value, assign_ms=d[1].value, finish_ms=d[2].value)

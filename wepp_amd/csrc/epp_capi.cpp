@@ -17,49 +17,11 @@
 #include <vector>
 
 #include "epp.hpp"
+#include "epp_host.hpp"
 #include "handle.hpp"
 #include "staged_copy.hpp"
 
 namespace {
-
-struct DevPool {                       // device allocations of one call, taken from / returned to the handle's cache
-    wepp_mat_t* mat;
-    std::vector<std::pair<void*, size_t>> used;
-    explicit DevPool(wepp_mat_t* m) : mat(m) {}
-    ~DevPool() {
-        // (a call that fails half-way may still have kernels in flight on these blocks)
-        (void)hipDeviceSynchronize();
-        for (auto& b : used) mat->epp_cache.blocks.push_back(b);
-    }
-    template <typename T>
-    hipError_t get(T** out, size_t n) {
-        const size_t bytes = (std::max<size_t>(n * sizeof(T), 64) + 255) & ~(size_t)255;
-        // the smallest cached block that holds the request without wasting more than half of itself
-        size_t best = SIZE_MAX;
-        auto& cache = mat->epp_cache.blocks;
-        for (size_t i = 0; i < cache.size(); i++) {
-            const size_t sz = cache[i].second;
-            if (sz >= bytes && sz <= 2 * bytes + (1u << 20) && (best == SIZE_MAX || sz < cache[best].second)) best = i;
-        }
-        if (best != SIZE_MAX) {
-            used.push_back(cache[best]);
-            cache.erase(cache.begin() + (std::ptrdiff_t)best);
-            *out = (T*)used.back().first;
-            return hipSuccess;
-        }
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess && !cache.empty()) {
-            // out of memory with blocks of other sizes parked in the cache: release them and try again
-            for (auto& b : cache) (void)hipFree(b.first);
-            cache.clear();
-            e = hipMalloc(&p, bytes);
-        }
-        if (e == hipSuccess) used.emplace_back(p, bytes);
-        *out = (T*)p;
-        return e;
-    }
-};
 
 // jobs (tile, stream chunk) a call aims at (WEPP_EPP_TARGET_JOBS): see wepp_epp_map
 constexpr uint32_t EPP_TARGET_JOBS = 262144;   // measured at 16 M nodes, 1 M reads: 8192 (one chunk per tile, 15.6 K jobs) 576 ms, 32 K 440, 64 K 402, 128 K 382, 256 K 370, 1 M 362, 4 M 379 ms on the device
@@ -67,6 +29,67 @@ struct EppTiming { float select_ms = 0, sweep1_ms = 0, sweep2_ms = 0, finish_ms 
 thread_local EppTiming g_last;
 
 }  // namespace
+
+namespace wepp {
+
+int epp_validate_reads(const wepp_epp_reads* rd, long long* total_degree_out) {
+    const uint32_t R = rd->n_reads;
+    long long total_degree = 0;
+    for (uint32_t r = 0; r < R; r++) {
+        if (rd->read_off[r + 1] < rd->read_off[r]) return set_error(WEPP_EINVAL, "read_off is not monotone");
+        if (rd->start[r] < 1 || rd->end[r] < rd->start[r] || (uint32_t)rd->end[r] > WEPP_MAX_POSITION)
+            return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": window must satisfy 1 <= start <= end <= 2^20 - 2");
+        if (rd->degree[r] < 0) return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": negative degree");
+        total_degree += rd->degree[r];
+        uint32_t prev = 0;
+        for (uint32_t j = rd->read_off[r]; j < rd->read_off[r + 1]; j++) {
+            const uint32_t w = rd->read_word[j];
+            const uint32_t pos = w & 0xFFFFFu, ref = (w >> 20) & 15u, mut = (w >> 24) & 15u;
+            if (pos == 0 || pos > WEPP_MAX_POSITION || pos <= prev)
+                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": mutations must be sorted by position, unique, in 1..2^20-2");
+            if (mut == ref || mut == 0)
+                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": a listed mutation must differ from the reference base (sam2pb.cpp:521-535)");
+            prev = pos;
+        }
+    }
+    if (total_degree_out) *total_degree_out = total_degree;
+    return WEPP_OK;
+}
+
+// order by (start, end, index).  Window bounds are genome positions: two stable counting passes (end,
+// then start) instead of a comparison sort through two indirections (≈0.1 s per 1 M reads)
+void epp_window_order(const wepp_epp_reads* rd, std::vector<uint32_t>& order) {
+    const uint32_t R = rd->n_reads;
+    order.resize(R);
+    int32_t lo = 0, hi = 0;
+    for (uint32_t r = 0; r < R; r++) {
+        lo = std::min({lo, rd->start[r], rd->end[r]});
+        hi = std::max({hi, rd->start[r], rd->end[r]});
+    }
+    if (lo < 0 || (uint64_t)hi > (1ull << 24)) {          // not positions: the general way
+        std::iota(order.begin(), order.end(), 0u);
+        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+            if (rd->start[a] != rd->start[b]) return rd->start[a] < rd->start[b];
+            if (rd->end[a] != rd->end[b]) return rd->end[a] < rd->end[b];
+            return a < b;
+        });
+    } else {
+        std::vector<uint32_t> tmp(R), cnt((size_t)hi + 2);
+        auto pass = [&](const int32_t* key, const uint32_t* in, uint32_t* out) {
+            std::fill(cnt.begin(), cnt.end(), 0u);
+            for (uint32_t s = 0; s < R; s++) cnt[(size_t)key[in ? in[s] : s] + 1]++;
+            for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
+            for (uint32_t s = 0; s < R; s++) {
+                const uint32_t r = in ? in[s] : s;
+                out[cnt[(size_t)key[r]]++] = r;
+            }
+        };
+        pass(rd->end, nullptr, tmp.data());
+        pass(rd->start, tmp.data(), order.data());
+    }
+}
+
+}  // namespace wepp
 
 extern "C" int wepp_mat_dfs_order(const wepp_mat_t* mat, uint32_t* ids) {
     if (!mat || !ids) return set_error(WEPP_EINVAL, "null argument");
@@ -103,23 +126,7 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
 
     // ---- validation (the reference's preconditions, made explicit) ----------------------
     long long total_degree = 0;
-    for (uint32_t r = 0; r < R; r++) {
-        if (rd->read_off[r + 1] < rd->read_off[r]) return set_error(WEPP_EINVAL, "read_off is not monotone");
-        if (rd->start[r] < 1 || rd->end[r] < rd->start[r] || (uint32_t)rd->end[r] > WEPP_MAX_POSITION)
-            return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": window must satisfy 1 <= start <= end <= 2^20 - 2");
-        if (rd->degree[r] < 0) return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": negative degree");
-        total_degree += rd->degree[r];
-        uint32_t prev = 0;
-        for (uint32_t j = rd->read_off[r]; j < rd->read_off[r + 1]; j++) {
-            const uint32_t w = rd->read_word[j];
-            const uint32_t pos = w & 0xFFFFFu, ref = (w >> 20) & 15u, mut = (w >> 24) & 15u;
-            if (pos == 0 || pos > WEPP_MAX_POSITION || pos <= prev)
-                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": mutations must be sorted by position, unique, in 1..2^20-2");
-            if (mut == ref || mut == 0)
-                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": a listed mutation must differ from the reference base (sam2pb.cpp:521-535)");
-            prev = pos;
-        }
-    }
+    if (int rc = epp_validate_reads(rd, &total_degree)) return rc;
     if (R == 0) {
         std::fill(out->hap_score, out->hap_score + N, 0.0);
         if (out->hap_read_counts) std::fill(out->hap_read_counts, out->hap_read_counts + (size_t)N * EPP_BINS, 0);
@@ -131,37 +138,8 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     hipStream_t stream = nullptr;
 
     // ---- reads in window order, tiles, groups ------------------------------------------
-    // order by (start, end, index).  Window bounds are genome positions: two stable counting passes (end,
-    // then start) instead of a comparison sort through two indirections (≈0.1 s per 1 M reads)
-    std::vector<uint32_t> order(R);
-    {
-        int32_t lo = 0, hi = 0;
-        for (uint32_t r = 0; r < R; r++) {
-            lo = std::min({lo, rd->start[r], rd->end[r]});
-            hi = std::max({hi, rd->start[r], rd->end[r]});
-        }
-        if (lo < 0 || (uint64_t)hi > (1ull << 24)) {          // not positions: the general way
-            std::iota(order.begin(), order.end(), 0u);
-            std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-                if (rd->start[a] != rd->start[b]) return rd->start[a] < rd->start[b];
-                if (rd->end[a] != rd->end[b]) return rd->end[a] < rd->end[b];
-                return a < b;
-            });
-        } else {
-            std::vector<uint32_t> tmp(R), cnt((size_t)hi + 2);
-            auto pass = [&](const int32_t* key, const uint32_t* in, uint32_t* out) {
-                std::fill(cnt.begin(), cnt.end(), 0u);
-                for (uint32_t s = 0; s < R; s++) cnt[(size_t)key[in ? in[s] : s] + 1]++;
-                for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
-                for (uint32_t s = 0; s < R; s++) {
-                    const uint32_t r = in ? in[s] : s;
-                    out[cnt[(size_t)key[r]]++] = r;
-                }
-            };
-            pass(rd->end, nullptr, tmp.data());
-            pass(rd->start, tmp.data(), order.data());
-        }
-    }
+    std::vector<uint32_t> order;
+    epp_window_order(rd, order);
     // reads per lane.  4 shares the serial per-event work (broadcasts, flips, atomics) among 256 reads
     // per wave, but a tile that large lists almost every position of its window, so every event takes
     // the allele-lookup path: measured 1.4x slower than 1 -- kept selectable for

@@ -1,19 +1,29 @@
 // wepp_epp_cli.cpp -- `wepp-epp`: the data path of `wepp detectPeaks` up to and including
 // wepp_filter::cartesian_map, on files: MAT .pb[.gz] + reads .pb (sam.proto, as written by
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
-//   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump]
+//   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE]
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
+// --assign FILE: FILE names the selected haplotypes, one identifier of a condensed node per line (anything after a
+// tab or comma is ignored; an unknown or repeated identifier is an error).  After the map the reads are assigned to
+// their nearest selected haplotypes (arena::dump_read2haplotype_mapping, arena.cpp:590-696, without the SAM files):
+//         <outdir>/haplotype_reads.csv     one row per selected haplotype that has a read, in the order of FILE:
+//                                          id,name,name,... -- the names reverse_merge (the reads file's column table) lists
+//                                          for its reads, reads in input order.  The reference's row and
+//                                          name order follow its hash map and thread schedule; this order is ours.
+//         <outdir>/haplotype_coverage.csv  one row per selected haplotype: id,fraction as std::to_string prints it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <string>
+#include <unordered_set>
 
 #include "wepp_filter.hpp"
 
 int main(int argc, char** argv) {
-    std::string mat_f, reads_f, ref_f, mask_f, outdir = ".";
+    std::string mat_f, reads_f, ref_f, mask_f, assign_f, outdir = ".";
     int device = 0;
     bool dump = false;
     for (int i = 1; i < argc; i++) {
@@ -28,10 +38,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "-d")) outdir = need("-d");
         else if (!strcmp(argv[i], "--device")) device = atoi(need("--device"));
         else if (!strcmp(argv[i], "--dump")) dump = true;
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N]\n"); return 1; }
+        else if (!strcmp(argv[i], "--assign")) assign_f = need("--assign");
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE]\n");
         return 1;
     }
     try {
@@ -60,6 +71,26 @@ int main(int argc, char** argv) {
                 printf("node %s %s\n", n->identifier.c_str(), n->parent ? n->parent->identifier.c_str() : "-");
             return 0;
         }
+        // the selection is checked before the device is touched
+        std::vector<MAT::Node*> selected;
+        std::vector<std::string> selected_ids;
+        if (!assign_f.empty()) {
+            std::ifstream in(assign_f);
+            if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", assign_f.c_str()); return 1; }
+            std::unordered_set<std::string> seen;
+            std::string line;
+            while (std::getline(in, line)) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                line = line.substr(0, line.find_first_of("\t,"));
+                if (line.empty()) continue;
+                MAT::Node* n = condensed.get_node(line);
+                if (!n) { fprintf(stderr, "ERROR: %s: %s is not a haplotype of the condensed tree\n", assign_f.c_str(), line.c_str()); return 1; }
+                if (!seen.insert(line).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", assign_f.c_str(), line.c_str()); return 1; }
+                selected.push_back(n);
+                selected_ids.push_back(line);
+            }
+            if (selected.empty()) { fprintf(stderr, "ERROR: %s names no haplotype\n", assign_f.c_str()); return 1; }
+        }
         cartesian_map_result res;
         if (cartesian_map(condensed, reads, reference.size(), res, device) != 0) return 1;
         FILE* f = fopen((outdir + "/haplotype_scores.tsv").c_str(), "w");
@@ -76,6 +107,27 @@ int main(int argc, char** argv) {
             fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\n", reads[r].read.c_str(), reads[r].start, reads[r].end, reads[r].degree,
                     res.max_parismony[r], res.parsimony_multiplicity[r]);
         fclose(f);
+        if (!selected.empty()) {
+            read2haplotype_result asg;
+            if (read2haplotype_mapping(condensed, reads, reference.size(), selected, asg, device) != 0) return 1;
+            f = fopen((outdir + "/haplotype_reads.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t k = 0; k < selected.size(); k++) {
+                if (asg.reads[k].empty()) continue;
+                std::string row = selected_ids[k];
+                for (int r : asg.reads[k]) {
+                    auto it = reverse_merge.find(reads[(size_t)r].read);       // arena.cpp:628
+                    if (it != reverse_merge.end()) for (auto const& name : it->second) row += "," + name;
+                }
+                fprintf(f, "%s\n", row.c_str());
+            }
+            fclose(f);
+            f = fopen((outdir + "/haplotype_coverage.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t k = 0; k < selected.size(); k++)
+                fprintf(f, "%s,%s\n", selected_ids[k].c_str(), std::to_string(asg.coverage[k]).c_str());   // arena.cpp:681-688
+            fclose(f);
+        }
     } catch (const std::exception& e) {
         fprintf(stderr, "%s\n", e.what());
         return 1;

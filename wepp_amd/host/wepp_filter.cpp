@@ -184,14 +184,16 @@ MAT::Tree create_condensed_tree(MAT::Node* ref_root, const std::unordered_set<in
     return T;
 }
 
-int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
-                  cartesian_map_result& out, int device) {
+namespace {
+
+// the condensed tree as a device handle: node ids = BFS order (children of a node ascending = stored order), as in
+// usher_place.cpp; bfs receives the nodes in that order
+int make_handle(MAT::Tree& condensed, int device, std::vector<MAT::Node*>& bfs, wepp_mat_t** mat) {
     if (!condensed.root) {
         fprintf(stderr, "ERROR: empty tree!\n");
         return 1;
     }
-    // node ids = BFS order (children of a node ascending = stored order), as in usher_place.cpp
-    std::vector<MAT::Node*> bfs = condensed.breadth_first_expansion();
+    bfs = condensed.breadth_first_expansion();
     const size_t N = bfs.size();
     std::unordered_map<const MAT::Node*, int32_t> id;
     id.reserve(N * 2);
@@ -213,22 +215,38 @@ int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size
     }
     wepp_tree_desc desc{(uint32_t)N, parent.data(), mut_off.data(), mut_pos.data(), mut_ref.data(), mut_par.data(),
                         mut_mut.data()};
-    wepp_mat_t* mat = nullptr;
-    if (wepp_mat_create(&desc, device, &mat) != WEPP_OK) {
+    if (wepp_mat_create(&desc, device, mat) != WEPP_OK) {
         fprintf(stderr, "ERROR: %s\n", wepp_last_error());
         return 1;
     }
-    const size_t R = reads.size();
-    std::vector<uint32_t> off(1, 0), words;
-    std::vector<int32_t> start(R), end(R), degree(R);
-    for (size_t r = 0; r < R; r++) {
-        for (const MAT::Mutation& m : reads[r].mutations)
-            words.push_back(wepp_pack_read_word((uint32_t)m.position, (uint32_t)m.ref_nuc, (uint32_t)m.mut_nuc,
-                                                m.mut_nuc == 0b1111 ? 1u : 0u));
-        off.push_back((uint32_t)words.size());
-        start[r] = reads[r].start; end[r] = reads[r].end; degree[r] = reads[r].degree;
+    return 0;
+}
+
+struct packed_reads {                // raw_reads as a wepp_epp_reads batch
+    std::vector<uint32_t> off{0}, words;
+    std::vector<int32_t> start, end, degree;
+    explicit packed_reads(const std::vector<raw_read>& reads) : start(reads.size()), end(reads.size()), degree(reads.size()) {
+        for (size_t r = 0; r < reads.size(); r++) {
+            for (const MAT::Mutation& m : reads[r].mutations)
+                words.push_back(wepp_pack_read_word((uint32_t)m.position, (uint32_t)m.ref_nuc, (uint32_t)m.mut_nuc,
+                                                    m.mut_nuc == 0b1111 ? 1u : 0u));
+            off.push_back((uint32_t)words.size());
+            start[r] = reads[r].start; end[r] = reads[r].end; degree[r] = reads[r].degree;
+        }
     }
-    wepp_epp_reads in{(uint32_t)R, off.data(), words.data(), start.data(), end.data(), degree.data()};
+    wepp_epp_reads view() const { return wepp_epp_reads{(uint32_t)start.size(), off.data(), words.data(), start.data(), end.data(), degree.data()}; }
+};
+
+}  // namespace
+
+int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                  cartesian_map_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    const size_t N = bfs.size(), R = reads.size();
+    packed_reads pr(reads);
+    wepp_epp_reads in = pr.view();
     std::vector<int32_t> pars(R), counts(N * NUM_RANGE_BINS);
     std::vector<uint32_t> mult(R), epp, order(N);
     std::vector<uint64_t> epp_off(R + 1);
@@ -264,5 +282,60 @@ int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size
     out.epp_positions_cache.assign(R, {});
     for (size_t r = 0; r < R; r++)
         out.epp_positions_cache[r].assign(epp.begin() + (long)epp_off[r], epp.begin() + (long)epp_off[r + 1]);
+    return 0;
+}
+
+int read2haplotype_mapping(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                           const std::vector<MAT::Node*>& selected, read2haplotype_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    const size_t N = bfs.size(), R = reads.size(), K = selected.size();
+    // arena index of every node: the inverse of wepp_mat_dfs_order over the BFS ids
+    std::vector<uint32_t> order(N), sel(K);
+    int rc = wepp_mat_dfs_order(mat, order.data());
+    if (rc == WEPP_OK) {
+        std::unordered_map<const MAT::Node*, uint32_t> arena;
+        arena.reserve(N * 2);
+        for (size_t k = 0; k < N; k++) arena[bfs[order[k]]] = (uint32_t)k;
+        for (size_t k = 0; k < K; k++) {
+            auto it = arena.find(selected[k]);
+            if (it == arena.end()) {
+                fprintf(stderr, "ERROR: selected haplotype %zu is not a node of the condensed tree\n", k);
+                wepp_mat_destroy(mat);
+                return 1;
+            }
+            sel[k] = it->second;
+        }
+    }
+    packed_reads pr(reads);
+    wepp_epp_reads in = pr.view();
+    std::vector<int32_t> min_dist(R);
+    std::vector<uint32_t> n_epp(R), lists(std::max<size_t>(R, 1) * 4), sel_reads(K), covered(K);
+    std::vector<uint64_t> off(R + 1, 0);
+    std::vector<int64_t> degree(K);
+    wepp_assign_out o{min_dist.data(), n_epp.data(), off.data(), lists.data(), lists.size(), sel_reads.data(), degree.data(),
+                      covered.data(), nullptr};
+    if (rc == WEPP_OK) rc = wepp_epp_assign(mat, &in, (uint32_t)genome_size, (uint32_t)K, sel.data(), &o);
+    if (rc == WEPP_ELIMIT && off[R] > lists.size()) {
+        // the guess was short: the sizes are known now, and a second call is cheap
+        lists.assign((size_t)off[R], 0);
+        o.asg_sel = lists.data();
+        o.asg_capacity = lists.size();
+        rc = wepp_epp_assign(mat, &in, (uint32_t)genome_size, (uint32_t)K, sel.data(), &o);
+    }
+    if (rc != WEPP_OK) fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+    wepp_mat_destroy(mat);
+    if (rc != WEPP_OK) return 1;
+    out.min_dist.assign(min_dist.begin(), min_dist.end());
+    out.reads.assign(K, {});
+    out.degree.assign(degree.begin(), degree.end());
+    out.coverage.resize(K);
+    for (size_t k = 0; k < K; k++) {
+        out.reads[k].reserve(sel_reads[k]);
+        out.coverage[k] = (double)covered[k] / (double)genome_size;      // arena.cpp:683-684
+    }
+    for (size_t r = 0; r < R; r++)                                      // ascending read index per haplotype
+        for (uint64_t j = off[r]; j < off[r + 1]; j++) out.reads[lists[(size_t)j]].push_back((int)r);
     return 0;
 }

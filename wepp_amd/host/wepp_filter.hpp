@@ -1,6 +1,7 @@
 // wepp_filter.hpp -- host-side mirror of the slice of WEPP's own interface that feeds and
 // consumes wepp_filter::cartesian_map (/root/reference/src/WEPP/): raw_read, the reads .pb
-// loader, read masking, the condensed tree, and the call itself on top of wepp_epp_map.
+// loader, read masking, the condensed tree, the call itself on top of wepp_epp_map, and the
+// read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign.
 // Same names and argument meaning as the reference; errors throw MAT::mat_error.
 #pragma once
 #include <array>
@@ -58,3 +59,17 @@ struct cartesian_map_result {
 // returns 0, or 1 after printing the error (the reference's convention for this layer)
 int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
                   cartesian_map_result& out, int device = 0);
+
+// what the read loop of arena::dump_read2haplotype_mapping computes (arena.cpp:610-667), per SELECTED haplotype, in
+// the order of `selected` (the reference's `abundance` order): the reads whose set of nearest selected haplotypes
+// (haplotype::mutation_distance, haplotype.hpp:123-177) holds it, as ascending indices into `reads`, the sum of
+// their degree (the count of :859-865), and the fraction of the genome they cover (:637-665, :683-684)
+struct read2haplotype_result {
+    std::vector<int> min_dist;                                   // per read: distance to its nearest selected haplotypes
+    std::vector<std::vector<int>> reads;                         // per selected haplotype
+    std::vector<long long> degree;
+    std::vector<double> coverage;
+};
+// `selected`: nodes of `condensed`, distinct.  Returns 0, or 1 after printing the error.
+int read2haplotype_mapping(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                           const std::vector<MAT::Node*>& selected, read2haplotype_result& out, int device = 0);
