@@ -517,6 +517,61 @@ int wepp_epp_assign(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t genom
  * genotype table, reads x selection (k_assign), lists + coverage counts */
 int wepp_epp_assign_last_timing(double *tables_ms, double *assign_ms, double *finish_ms);
 
+/* ---- residual mutations against a selection of haplotypes ------------------ *
+ * Replaces arena::resolve_unaccounted_mutations (src/WEPP/arena.cpp:739-892) up to its two files: which
+ * reads carry each residual mutation (an allele seen in the reads that the selected haplotypes do not
+ * explain) and which selected haplotypes it most plausibly belongs to.  `mat`, `reads`, `genome_size` and
+ * `sel` are those of wepp_epp_assign; res_word[0 .. n_res) are the residual mutations IN THE CALLER'S ORDER,
+ * each wepp_pack_read_word(position, ref_nuc, mut_nuc, 0): ref_nuc the one-hot mask of the reference base at
+ * the position, mut_nuc the residual allele's mask, 1 .. 14.
+ * For every read r start from a copy r' of its entries and visit the m with start <= pos(m) <= end in
+ * increasing m (the reference's copy_if order; it matters when two residual mutations share a position):
+ *   r' has an entry at pos(m) that is not N: if its mut_nuc == mut_nuc(m) the entry becomes N and r is
+ *     COVERED for m (:765-770); otherwise nothing happens;
+ *   r' has an N entry at pos(m) -- also one an earlier m' at the position has just made --: r is MASKED
+ *     for m (:773-775);
+ *   r' has no entry at pos(m): if mut_nuc(m) == ref_nuc(m) an N entry is inserted in position order and r
+ *     is covered (:780-790); otherwise nothing happens.
+ * The final r' stands for r under every m it is covered or masked for (:794-807); a read with no relation
+ * takes no further part.  With S(m) the covered and masked reads of m and epps(r') the k minimising
+ * wepp_epp_assign's d(r', k):
+ *   rel_off/rel_read   S(m) as a CSR over the mutations: read indices ascending within a mutation, bit 31
+ *                      set = masked, clear = covered; both or neither, rel_off alone with rel_capacity = 0
+ *                      asks for the sizes only
+ *   n_covered[M], n_masked[M]
+ *   hap_reads[M * K]   reads of S(m) whose epps hold k; may be NULL
+ *   hap_degree[M * K]  sum of their degree (:859-865); may be NULL
+ *   best_degree[M]     max of hap_degree[m][k] over the k with hap_reads[m][k] > 0; 0 when S(m) is empty
+ *   best_mask          [M * ceil(K / 32)], bit k & 31 of word k / 32: hap_reads[m][k] > 0 and hap_degree[m][k]
+ *                      == best_degree[m] (the reference's map only holds haplotypes that appeared, :859-884:
+ *                      a mutation whose reads all have degree 0 lists those, not all K)
+ *   n_touched[1]       reads with at least one relation
+ * Everything is integer: bit-identical run to run.  Read shards: hap_reads / hap_degree add, best_* must be
+ * recomputed from the sums.  The argument checks on reads and selection and the table limits are
+ * wepp_epp_assign's.  WEPP_EINVAL besides: a residual position outside 1 .. genome_size, mut_nuc 0 or 15,
+ * ref_nuc not one-hot.  WEPP_ELIMIT besides: n_reads >= 2^31; 2^32 or more entries in the touched reads
+ * after the insertions; rel_capacity < rel_off[n_res] -- then EVERY other output is delivered and rel_off is
+ * filled, as with asg_sel.  n_res == 0, n_reads == 0 or no touched read: WEPP_OK, zeroed outputs, rel_off all
+ * 0, no assignment is launched.  Serial per handle. */
+typedef struct {
+    uint64_t *rel_off;      /* [n_res + 1] */
+    uint32_t *rel_read;     /* [rel_capacity] */
+    uint64_t rel_capacity;
+    uint32_t *n_covered;    /* [n_res] */
+    uint32_t *n_masked;     /* [n_res] */
+    int64_t  *best_degree;  /* [n_res] */
+    uint32_t *best_mask;    /* [n_res * ceil(n_sel / 32)] */
+    uint32_t *hap_reads;    /* [n_res * n_sel] or NULL */
+    int64_t  *hap_degree;   /* [n_res * n_sel] or NULL */
+    uint32_t *n_touched;    /* [1] */
+} wepp_resolve_out;
+int wepp_epp_resolve(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t genome_size,
+                     uint32_t n_sel, const uint32_t *sel,
+                     uint32_t n_res, const uint32_t *res_word, wepp_resolve_out *out);
+/* device time of the calling thread's last wepp_epp_resolve by phase (HIP events, ms): marking the reads and
+ * ordering the relations, the selection's genotype table, k_assign on the touched reads, tally + best */
+int wepp_epp_resolve_last_timing(double *mark_ms, double *tables_ms, double *assign_ms, double *tally_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

@@ -133,6 +133,13 @@ class AssignOutC(ctypes.Structure):
                 ("sel_degree", ctypes.c_void_p), ("sel_covered", ctypes.c_void_p), ("cover_bits", ctypes.c_void_p)]
 
 
+class ResolveOutC(ctypes.Structure):
+    _fields_ = [("rel_off", ctypes.c_void_p), ("rel_read", ctypes.c_void_p), ("rel_capacity", ctypes.c_uint64),
+                ("n_covered", ctypes.c_void_p), ("n_masked", ctypes.c_void_p), ("best_degree", ctypes.c_void_p),
+                ("best_mask", ctypes.c_void_p), ("hap_reads", ctypes.c_void_p), ("hap_degree", ctypes.c_void_p),
+                ("n_touched", ctypes.c_void_p)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -185,6 +192,9 @@ _SIGS = {
     "wepp_epp_assign": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.c_uint32, _V,
                                        ctypes.POINTER(AssignOutC)]),
     "wepp_epp_assign_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+    "wepp_epp_resolve": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.c_uint32, _V,
+                                        ctypes.c_uint32, _V, ctypes.POINTER(ResolveOutC)]),
+    "wepp_epp_resolve_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

@@ -556,6 +556,60 @@ class Mat:
             out["cover_bits"] = bits
         return out
 
+    def epp_resolve(self, reads, genome_size, sel, residual, want_lists=True, want_tallies=False, rel_capacity=None):
+        """wepp_epp_resolve: the residual mutations `residual` (packed words pack_read_word(pos, ref, mut), or a list
+        of (pos, ref, mut), in the caller's order) against the reads and the selected haplotypes sel.  Returns
+        n_covered / n_masked / best_degree per mutation, best_mask [M, ceil(K / 32)], best (per mutation the indices
+        INTO sel of best_mask, ascending), n_touched, with want_lists rel_off / rel_read (CSR of the covered and
+        masked reads, bit 31 = masked) and with want_tallies hap_reads / hap_degree [M, K]."""
+        R = reads.n_reads
+        sel = np.ascontiguousarray(sel, dtype=np.uint32)
+        K = int(sel.size)
+        if isinstance(residual, np.ndarray):
+            res = np.ascontiguousarray(residual, dtype=np.uint32)
+        else:
+            res = np.array([int(pack_read_word(p, r, m)) for p, r, m in residual], dtype=np.uint32)
+        M = int(res.size)
+        KW = (K + 31) // 32
+        ncov = np.zeros(max(M, 1), np.uint32); nmask = np.zeros(max(M, 1), np.uint32)
+        bdeg = np.zeros(max(M, 1), np.int64); bmask = np.zeros((M, KW), np.uint32)
+        hreads = np.zeros((M, K), np.uint32) if want_tallies else None
+        hdeg = np.zeros((M, K), np.int64) if want_tallies else None
+        ntouched = np.zeros(1, np.uint32)
+        # a guess: a read meets a few residual mutations
+        cap = int(rel_capacity if rel_capacity is not None else 4 * max(R, 1))
+        roff = np.zeros(M + 1, np.uint64) if want_lists else None
+        rrel = np.zeros(max(cap, 1), np.uint32) if want_lists else None
+        rw = reads.read_word if reads.read_word.size else np.zeros(1, np.uint32)
+        rd = _lib.EppReadsC(R, _ptr(reads.read_off).value, _ptr(rw).value, _ptr(reads.start).value,
+                            _ptr(reads.end).value, _ptr(reads.degree).value)
+
+        def call():
+            o = _lib.ResolveOutC(_ptr(roff).value if want_lists else None, _ptr(rrel).value if want_lists else None, cap,
+                                 _ptr(ncov).value, _ptr(nmask).value, _ptr(bdeg).value,
+                                 _ptr(bmask).value if bmask.size else None,
+                                 _ptr(hreads).value if want_tallies and hreads.size else None,
+                                 _ptr(hdeg).value if want_tallies and hdeg.size else None, _ptr(ntouched).value)
+            return lib.wepp_epp_resolve(self._h, ctypes.byref(rd), int(genome_size), K, _ptr(sel) if K else None,
+                                        M, _ptr(res) if M else None, ctypes.byref(o))
+        rc = call()
+        if rc == 4 and want_lists and int(roff[M]) > cap:
+            # the guess was short: rel_off[M] is the size
+            cap = int(roff[M])
+            rrel = np.zeros(cap, np.uint32)
+            rc = call()
+        check(rc)
+        bits = np.unpackbits(bmask.view(np.uint8), axis=1, bitorder="little")[:, :K] if M else np.zeros((0, K), np.uint8)
+        out = dict(n_covered=ncov[:M], n_masked=nmask[:M], best_degree=bdeg[:M], best_mask=bmask,
+                   best=[np.flatnonzero(b).astype(np.uint32) for b in bits], n_touched=int(ntouched[0]))
+        if want_lists:
+            out["rel_off"] = roff
+            out["rel_read"] = rrel[: int(roff[M])]
+        if want_tallies:
+            out["hap_reads"] = hreads
+            out["hap_degree"] = hdeg
+        return out
+
     def imputed_mutations(self, reads, best_bfs_j):
         """Per read: list of (position, nucleotide mask) imputed for its ambiguous entries at
         the chosen node (column 4 of placement_stats.tsv): wepp_imputed_mutations."""
@@ -646,3 +700,10 @@ def epp_assign_last_timing():
     d = [ctypes.c_double() for _ in range(3)]
     check(lib.wepp_epp_assign_last_timing(*[ctypes.byref(x) for x in d]))
     return dict(tables_ms=d[0].value, assign_ms=d[1].value, finish_ms=d[2].value)
+
+
+def epp_resolve_last_timing():
+    """Device time by phase (ms) of this thread's last Mat.epp_resolve call."""
+    d = [ctypes.c_double() for _ in range(4)]
+    check(lib.wepp_epp_resolve_last_timing(*[ctypes.byref(x) for x in d]))
+    return dict(mark_ms=d[0].value, tables_ms=d[1].value, assign_ms=d[2].value, tally_ms=d[3].value)

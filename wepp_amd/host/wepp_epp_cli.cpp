@@ -1,7 +1,7 @@
 // wepp_epp_cli.cpp -- `wepp-epp`: the data path of `wepp detectPeaks` up to and including
 // wepp_filter::cartesian_map, on files: MAT .pb[.gz] + reads .pb (sam.proto, as written by
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
-//   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE]
+//   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE [--resolve RESIDUAL]]
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
@@ -13,6 +13,17 @@
 //                                          for its reads, reads in input order.  The reference's row and
 //                                          name order follow its hash map and thread schedule; this order is ours.
 //         <outdir>/haplotype_coverage.csv  one row per selected haplotype: id,fraction as std::to_string prints it.
+// --resolve RESIDUAL (with --assign only): RESIDUAL is the reference's residual_mutations.txt, one line
+// `<pos><letter>,<v1>[,<v2>...]` per residual mutation (residual_file.hpp says what is refused).  The residual mutations
+// are attributed to the selected haplotypes (arena::resolve_unaccounted_mutations, arena.cpp:698-904):
+//         <outdir>/mutation_reads.csv      one row per residual mutation that a read carries: key,name,name,... -- key =
+//                                          `<pos><letter>:<v1>:<v2>...`, then the names reverse_merge lists for the reads
+//                                          that carry it, reads in input order.
+//         <outdir>/mutation_haplotypes.csv one row per residual mutation with a read that carries it or holds an N at
+//                                          its site: key,id,id,... -- the selected haplotypes its reads point to, in
+//                                          the order of FILE.
+//                                          The reference's row order in both files is that of a concurrent hash map and
+//                                          not defined; here the rows follow RESIDUAL.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,7 +34,7 @@
 #include "wepp_filter.hpp"
 
 int main(int argc, char** argv) {
-    std::string mat_f, reads_f, ref_f, mask_f, assign_f, outdir = ".";
+    std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, outdir = ".";
     int device = 0;
     bool dump = false;
     for (int i = 1; i < argc; i++) {
@@ -39,10 +50,15 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--device")) device = atoi(need("--device"));
         else if (!strcmp(argv[i], "--dump")) dump = true;
         else if (!strcmp(argv[i], "--assign")) assign_f = need("--assign");
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE]\n"); return 1; }
+        else if (!strcmp(argv[i], "--resolve")) resolve_f = need("--resolve");
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]]\n");
+        return 1;
+    }
+    if (!resolve_f.empty() && assign_f.empty()) {
+        fprintf(stderr, "ERROR: --resolve needs --assign: residual mutations are attributed to the selected haplotypes\n");
         return 1;
     }
     try {
@@ -91,6 +107,9 @@ int main(int argc, char** argv) {
             }
             if (selected.empty()) { fprintf(stderr, "ERROR: %s names no haplotype\n", assign_f.c_str()); return 1; }
         }
+        // so is the residual list
+        std::vector<residual_mutation> residual;
+        if (!resolve_f.empty()) residual = load_residual_mutations(resolve_f, reference);
         cartesian_map_result res;
         if (cartesian_map(condensed, reads, reference.size(), res, device) != 0) return 1;
         FILE* f = fopen((outdir + "/haplotype_scores.tsv").c_str(), "w");
@@ -126,6 +145,31 @@ int main(int argc, char** argv) {
             if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
             for (size_t k = 0; k < selected.size(); k++)
                 fprintf(f, "%s,%s\n", selected_ids[k].c_str(), std::to_string(asg.coverage[k]).c_str());   // arena.cpp:681-688
+            fclose(f);
+        }
+        if (!resolve_f.empty()) {
+            resolve_result rr;
+            if (resolve_unaccounted_mutations(condensed, reads, reference.size(), selected, residual, rr, device) != 0) return 1;
+            f = fopen((outdir + "/mutation_reads.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t m = 0; m < residual.size(); m++) {
+                if (rr.covered_reads[m].empty()) continue;
+                std::string row = residual[m].key;
+                for (int r : rr.covered_reads[m]) {
+                    auto it = reverse_merge.find(reads[(size_t)r].read);       // arena.cpp:816
+                    if (it != reverse_merge.end()) for (auto const& name : it->second) row += "," + name;
+                }
+                fprintf(f, "%s\n", row.c_str());
+            }
+            fclose(f);
+            f = fopen((outdir + "/mutation_haplotypes.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t m = 0; m < residual.size(); m++) {
+                if (rr.covered_reads[m].empty() && rr.n_masked[m] == 0) continue;
+                std::string row = residual[m].key;
+                for (int k : rr.best[m]) row += "," + selected_ids[(size_t)k];       // arena.cpp:895-903
+                fprintf(f, "%s\n", row.c_str());
+            }
             fclose(f);
         }
     } catch (const std::exception& e) {

@@ -285,29 +285,46 @@ int cartesian_map(MAT::Tree& condensed, const std::vector<raw_read>& reads, size
     return 0;
 }
 
+namespace {
+
+// sel[k] = arena index of selected[k]: the inverse of wepp_mat_dfs_order over the BFS ids
+int arena_indices(wepp_mat_t* mat, const std::vector<MAT::Node*>& bfs, const std::vector<MAT::Node*>& selected,
+                  std::vector<uint32_t>& sel) {
+    const size_t N = bfs.size(), K = selected.size();
+    std::vector<uint32_t> order(N);
+    sel.assign(K, 0);
+    if (wepp_mat_dfs_order(mat, order.data()) != WEPP_OK) {
+        fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+        return 1;
+    }
+    std::unordered_map<const MAT::Node*, uint32_t> arena;
+    arena.reserve(N * 2);
+    for (size_t k = 0; k < N; k++) arena[bfs[order[k]]] = (uint32_t)k;
+    for (size_t k = 0; k < K; k++) {
+        auto it = arena.find(selected[k]);
+        if (it == arena.end()) {
+            fprintf(stderr, "ERROR: selected haplotype %zu is not a node of the condensed tree\n", k);
+            return 1;
+        }
+        sel[k] = it->second;
+    }
+    return 0;
+}
+
+}  // namespace
+
 int read2haplotype_mapping(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
                            const std::vector<MAT::Node*>& selected, read2haplotype_result& out, int device) {
     std::vector<MAT::Node*> bfs;
     wepp_mat_t* mat = nullptr;
     if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
-    const size_t N = bfs.size(), R = reads.size(), K = selected.size();
-    // arena index of every node: the inverse of wepp_mat_dfs_order over the BFS ids
-    std::vector<uint32_t> order(N), sel(K);
-    int rc = wepp_mat_dfs_order(mat, order.data());
-    if (rc == WEPP_OK) {
-        std::unordered_map<const MAT::Node*, uint32_t> arena;
-        arena.reserve(N * 2);
-        for (size_t k = 0; k < N; k++) arena[bfs[order[k]]] = (uint32_t)k;
-        for (size_t k = 0; k < K; k++) {
-            auto it = arena.find(selected[k]);
-            if (it == arena.end()) {
-                fprintf(stderr, "ERROR: selected haplotype %zu is not a node of the condensed tree\n", k);
-                wepp_mat_destroy(mat);
-                return 1;
-            }
-            sel[k] = it->second;
-        }
+    const size_t R = reads.size(), K = selected.size();
+    std::vector<uint32_t> sel;
+    if (arena_indices(mat, bfs, selected, sel) != 0) {
+        wepp_mat_destroy(mat);
+        return 1;
     }
+    int rc = WEPP_OK;
     packed_reads pr(reads);
     wepp_epp_reads in = pr.view();
     std::vector<int32_t> min_dist(R);
@@ -337,5 +354,57 @@ int read2haplotype_mapping(MAT::Tree& condensed, const std::vector<raw_read>& re
     }
     for (size_t r = 0; r < R; r++)                                      // ascending read index per haplotype
         for (uint64_t j = off[r]; j < off[r + 1]; j++) out.reads[lists[(size_t)j]].push_back((int)r);
+    return 0;
+}
+
+std::vector<residual_mutation> load_residual_mutations(std::string const& filename, std::string const& reference) {
+    std::ifstream in(filename);
+    if (!in.is_open()) throw mat_error("Error: Unable to open file " + filename);
+    return parse_residual_mutations(in, filename, reference);
+}
+
+int resolve_unaccounted_mutations(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                                  const std::vector<MAT::Node*>& selected, const std::vector<residual_mutation>& residual,
+                                  resolve_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    const size_t R = reads.size(), K = selected.size(), M = residual.size(), KW = (K + 31) / 32;
+    std::vector<uint32_t> sel;
+    if (arena_indices(mat, bfs, selected, sel) != 0) {
+        wepp_mat_destroy(mat);
+        return 1;
+    }
+    packed_reads pr(reads);
+    wepp_epp_reads in = pr.view();
+    std::vector<uint32_t> res(M), rel(std::max<size_t>(R, 1) * 4), n_cov(M), n_mask(M), best_mask(M * KW), touched(1);
+    for (size_t m = 0; m < M; m++)
+        res[m] = wepp_pack_read_word((uint32_t)residual[m].position, (uint32_t)residual[m].ref_nuc, (uint32_t)residual[m].mut_nuc, 0);
+    std::vector<uint64_t> off(M + 1, 0);
+    std::vector<int64_t> best_degree(M);
+    wepp_resolve_out o{off.data(), rel.data(), rel.size(), n_cov.data(), n_mask.data(), best_degree.data(), best_mask.data(),
+                       nullptr, nullptr, touched.data()};
+    int rc = wepp_epp_resolve(mat, &in, (uint32_t)genome_size, (uint32_t)K, sel.data(), (uint32_t)M, res.data(), &o);
+    if (rc == WEPP_ELIMIT && off[M] > rel.size()) {
+        // the guess was short: the sizes are known now
+        rel.assign((size_t)off[M], 0);
+        o.rel_read = rel.data();
+        o.rel_capacity = rel.size();
+        rc = wepp_epp_resolve(mat, &in, (uint32_t)genome_size, (uint32_t)K, sel.data(), (uint32_t)M, res.data(), &o);
+    }
+    if (rc != WEPP_OK) fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+    wepp_mat_destroy(mat);
+    if (rc != WEPP_OK) return 1;
+    out.covered_reads.assign(M, {});
+    out.n_masked.assign(n_mask.begin(), n_mask.end());
+    out.best.assign(M, {});
+    out.best_degree.assign(best_degree.begin(), best_degree.end());
+    for (size_t m = 0; m < M; m++) {
+        out.covered_reads[m].reserve(n_cov[m]);
+        for (uint64_t j = off[m]; j < off[m + 1]; j++)
+            if (!(rel[(size_t)j] >> 31)) out.covered_reads[m].push_back((int)rel[(size_t)j]);
+        for (size_t k = 0; k < K; k++)
+            if ((best_mask[m * KW + k / 32] >> (k & 31)) & 1u) out.best[m].push_back((int)k);
+    }
     return 0;
 }

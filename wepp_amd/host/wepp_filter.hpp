@@ -1,7 +1,8 @@
 // wepp_filter.hpp -- host-side mirror of the slice of WEPP's own interface that feeds and
 // consumes wepp_filter::cartesian_map (/root/reference/src/WEPP/): raw_read, the reads .pb
-// loader, read masking, the condensed tree, the call itself on top of wepp_epp_map, and the
-// read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign.
+// loader, read masking, the condensed tree, the call itself on top of wepp_epp_map, the
+// read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign, and
+// arena::resolve_unaccounted_mutations on top of wepp_epp_resolve.
 // Same names and argument meaning as the reference; errors throw MAT::mat_error.
 #pragma once
 #include <array>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "mat.hpp"
+#include "residual_file.hpp"
 
 static constexpr int NUM_RANGE_BINS = 50;          // src/WEPP/config.hpp:13
 static constexpr int MAX_CACHED_EPP_SIZE = 2048;   // src/WEPP/config.hpp:9
@@ -73,3 +75,23 @@ struct read2haplotype_result {
 // `selected`: nodes of `condensed`, distinct.  Returns 0, or 1 after printing the error.
 int read2haplotype_mapping(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
                            const std::vector<MAT::Node*>& selected, read2haplotype_result& out, int device = 0);
+
+// residual_mutations.txt (arena.cpp:708-731) -> the residual mutations in the order of the file; throws
+// MAT::mat_error (residual_file.hpp lists what is refused)
+std::vector<residual_mutation> load_residual_mutations(std::string const& filename, std::string const& reference);
+
+// what arena::resolve_unaccounted_mutations computes (arena.cpp:739-892), per residual mutation, in the order of
+// `residual`: the reads that carry it (ascending indices into `reads`; the rows of mutation_reads.csv), how many reads
+// hold an N at its site, and the selected haplotypes its reads point to (indices into `selected`, ascending: those
+// among the haplotypes nearest to some covered or masked read whose summed degree is the largest; the rows of
+// mutation_haplotypes.csv)
+struct resolve_result {
+    std::vector<std::vector<int>> covered_reads;
+    std::vector<size_t> n_masked;
+    std::vector<std::vector<int>> best;
+    std::vector<long long> best_degree;
+};
+// `selected`: nodes of `condensed`, distinct.  Returns 0, or 1 after printing the error.
+int resolve_unaccounted_mutations(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                                  const std::vector<MAT::Node*>& selected, const std::vector<residual_mutation>& residual,
+                                  resolve_result& out, int device = 0);
