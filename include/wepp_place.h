@@ -572,6 +572,53 @@ int wepp_epp_resolve(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t geno
  * ordering the relations, the selection's genotype table, k_assign on the touched reads, tally + best */
 int wepp_epp_resolve_last_timing(double *mark_ms, double *tables_ms, double *assign_ms, double *tally_ms);
 
+/* ---- haplotypes within a mutation radius of pivots ------------------------- *
+ * The primitive under arena::closest_neighbors and arena::highest_scoring_neighbors (src/WEPP/arena.cpp:171-249):
+ * all haplotypes within mutation distance `radius` of a pivot that are reachable from it through haplotypes
+ * within the radius.  piv[0 .. n_piv) are distinct arena indices.  With g_h(p) the allele mask of haplotype h at
+ * position p as arena::from_mat builds stack_muts (0 = the reference base, also after a back-mutation),
+ * haplotype::mutation_distance(haplotype*) (haplotype.hpp:179) is asymmetric where an allele is N (15); `form`
+ * chooses the direction the caller's loop uses:
+ *   WEPP_NBR_TO_PIVOT    D(n) = node->mutation_distance(pivot) = sum over p of [g_piv(p) != 15][g_n(p) != g_piv(p)]
+ *                        (closest_neighbors)
+ *   WEPP_NBR_FROM_PIVOT  D(n) = pivot->mutation_distance(node) = sum over p of [g_n(p) != 15][g_n(p) != g_piv(p)]
+ *                        (highest_scoring_neighbors)
+ * The REGION of a pivot is its connected component in the forest the tree induces on {n : D(n) <= radius}: what
+ * the reference's BFS over parent and children, and its climb followed by the pruned DFS, both enumerate.
+ *   nbr_off/nbr_node/nbr_dist  the regions as a CSR over the pivots (nbr_off[n_piv + 1]): arena indices
+ *                        ascending within a pivot, with their D.  Nodes with skip[n] != 0 are walked through but
+ *                        not listed (include_mapped = false); skip may be NULL.  The pivot itself is listed
+ *                        unless it is skipped.  nbr_off alone with nbr_capacity = 0 asks for the sizes only.
+ *   top[n_piv]           the highest ancestor of the pivot in its region; may be NULL
+ *   n_region[n_piv]      size of the region before `skip`; may be NULL
+ * The ranking by score and the num_limit truncation are the caller's, like the final sort of wepp_epp_map.
+ * Everything is integer and independent of the order of execution: bit-identical run to run.
+ * The pivots are processed in passes of as many as fit a device budget of 2 GiB (8 bytes per tree node and
+ * pivot); WEPP_NBR_PASS_COLS in the environment (diagnostic, read once per handle, changes no result) forces the
+ * number of pivots per pass.  WEPP_EINVAL: a null argument, n_piv == 0, an index >= n_nodes, a repeated pivot, an
+ * unknown form.  WEPP_ELIMIT: a tree of which not even 4 pivots fit the budget; the table limits of
+ * wepp_epp_assign for the pivots of a pass; nbr_capacity < nbr_off[n_piv] -- then EVERY other output is delivered,
+ * nbr_off is filled, and the caller calls again: nothing stays pending on the handle.  Serial per handle. */
+#define WEPP_NBR_TO_PIVOT   0
+#define WEPP_NBR_FROM_PIVOT 1
+typedef struct {
+    uint64_t *nbr_off;      /* [n_piv + 1] */
+    uint32_t *nbr_node;     /* [nbr_capacity] */
+    int32_t  *nbr_dist;     /* [nbr_capacity] */
+    uint64_t nbr_capacity;
+    uint32_t *top;          /* [n_piv] or NULL */
+    uint32_t *n_region;     /* [n_piv] or NULL */
+} wepp_neighbors_out;
+int wepp_epp_neighbors(wepp_mat_t *mat, uint32_t n_piv, const uint32_t *piv, uint32_t radius, int form,
+                       const uint8_t *skip /* [n_nodes] or NULL */, wepp_neighbors_out *out);
+/* the whole distance field, dist[k * n_nodes + n] = D(n) of pivot k: for small trees, tests and
+ * print_mutation_distance-style reports.  WEPP_ELIMIT beyond 2^28 cells (n_piv * n_nodes). */
+int wepp_epp_distances(wepp_mat_t *mat, uint32_t n_piv, const uint32_t *piv, int form, int32_t *dist);
+/* device time of the calling thread's last wepp_epp_neighbors / wepp_epp_distances by phase, summed over the
+ * passes (HIP events, ms): the pivots' genotype tables, the distance field (deltas + column scan), the regions
+ * (radius test, second scan, tops, counts, lists) */
+int wepp_epp_neighbors_last_timing(double *tables_ms, double *field_ms, double *region_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

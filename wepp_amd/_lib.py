@@ -140,6 +140,11 @@ class ResolveOutC(ctypes.Structure):
                 ("n_touched", ctypes.c_void_p)]
 
 
+class NeighborsOutC(ctypes.Structure):
+    _fields_ = [("nbr_off", ctypes.c_void_p), ("nbr_node", ctypes.c_void_p), ("nbr_dist", ctypes.c_void_p),
+                ("nbr_capacity", ctypes.c_uint64), ("top", ctypes.c_void_p), ("n_region", ctypes.c_void_p)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -195,6 +200,10 @@ _SIGS = {
     "wepp_epp_resolve": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.c_uint32, _V,
                                         ctypes.c_uint32, _V, ctypes.POINTER(ResolveOutC)]),
     "wepp_epp_resolve_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
+    "wepp_epp_neighbors": (ctypes.c_int, [_V, ctypes.c_uint32, _V, ctypes.c_uint32, ctypes.c_int, _V,
+                                          ctypes.POINTER(NeighborsOutC)]),
+    "wepp_epp_distances": (ctypes.c_int, [_V, ctypes.c_uint32, _V, ctypes.c_int, _V]),
+    "wepp_epp_neighbors_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

@@ -16,6 +16,7 @@ from ._lib import lib, check
 A, C, G, T, N = 1, 2, 4, 8, 15  # nucleotide masks, src/mutation_annotated_tree.cpp:19-74
 # how a read was placed (include/wepp_place.h WEPP_PLAN_*, Mat.last_plans)
 PLAN_WALK8, PLAN_WALK16, PLAN_SWEEP, PLAN_WALKC8, PLAN_WALKC16, PLAN_WIN, PLAN_SEED = range(7)
+NBR_TO_PIVOT, NBR_FROM_PIVOT = 0, 1  # wepp_epp_neighbors: the direction of mutation_distance (include/wepp_place.h)
 PLAN_NAMES = ("walk8", "walk16", "sweep", "walkc8", "walkc16", "window", "seed")
 WINDOW_CROWN_LEVELS = 7  # crowns per genome window at most (flatmat.hpp: WC_MAX; FlatView 'wc_tau' / 'wc_nodes' rows)
 WINDOW_CROWN_SLOT = 15   # stream slot of the window crowns in Mat.last_plans / last_tiers (Mat.last_crowns tells which crown)
@@ -610,6 +611,54 @@ class Mat:
             out["hap_degree"] = hdeg
         return out
 
+    def epp_neighbors(self, piv, radius, form, skip=None, nbr_capacity=None, want_lists=True):
+        """wepp_epp_neighbors: per pivot (distinct arena indices) the haplotypes within mutation distance `radius`
+        that are reachable from it through haplotypes within the radius.  form = NBR_TO_PIVOT
+        (node->mutation_distance(pivot), arena::closest_neighbors) or NBR_FROM_PIVOT (pivot->mutation_distance(node),
+        arena::highest_scoring_neighbors); skip = a byte per haplotype, nonzero = walked through but not listed.
+        Returns nbr_off / nbr_node / nbr_dist (CSR over the pivots, arena indices ascending), top and n_region;
+        want_lists=False asks for the sizes only (nbr_off, top, n_region)."""
+        piv = np.ascontiguousarray(piv, dtype=np.uint32)
+        K = int(piv.size)
+        if skip is not None:
+            skip = np.ascontiguousarray(skip, dtype=np.uint8)
+            if skip.size != self.n_nodes:
+                raise ValueError("skip holds one byte per haplotype")
+        off = np.zeros(K + 1, np.uint64)
+        top = np.zeros(max(K, 1), np.uint32); nreg = np.zeros(max(K, 1), np.uint32)
+        if not want_lists:
+            o = _lib.NeighborsOutC(_ptr(off).value, None, None, 0, _ptr(top).value, _ptr(nreg).value)
+            rc = lib.wepp_epp_neighbors(self._h, K, _ptr(piv) if K else None, int(radius), int(form),
+                                        _ptr(skip) if skip is not None else None, ctypes.byref(o))
+            if not (rc == 4 and K and int(off[K]) > 0):     # (WEPP_ELIMIT with the sizes filled is the answer)
+                check(rc)
+            return dict(nbr_off=off, top=top[:K], n_region=nreg[:K])
+        # a guess: a region is a few dozen haplotypes
+        cap = int(nbr_capacity if nbr_capacity is not None else 64 * max(K, 1))
+        node = np.zeros(max(cap, 1), np.uint32); dist = np.zeros(max(cap, 1), np.int32)
+
+        def call():
+            o = _lib.NeighborsOutC(_ptr(off).value, _ptr(node).value, _ptr(dist).value, cap, _ptr(top).value, _ptr(nreg).value)
+            return lib.wepp_epp_neighbors(self._h, K, _ptr(piv) if K else None, int(radius), int(form),
+                                          _ptr(skip) if skip is not None else None, ctypes.byref(o))
+        rc = call()
+        if rc == 4 and int(off[K]) > cap:
+            # the guess was short: nbr_off[K] is the size
+            cap = int(off[K])
+            node = np.zeros(cap, np.uint32); dist = np.zeros(cap, np.int32)
+            rc = call()
+        check(rc)
+        n = int(off[K])
+        return dict(nbr_off=off, nbr_node=node[:n], nbr_dist=dist[:n], top=top[:K], n_region=nreg[:K])
+
+    def epp_distances(self, piv, form):
+        """wepp_epp_distances: [len(piv), n_nodes] mutation distances between every pivot and every haplotype."""
+        piv = np.ascontiguousarray(piv, dtype=np.uint32)
+        K = int(piv.size)
+        dist = np.zeros((K, self.n_nodes), np.int32)
+        check(lib.wepp_epp_distances(self._h, K, _ptr(piv) if K else None, int(form), _ptr(dist) if dist.size else None))
+        return dist
+
     def imputed_mutations(self, reads, best_bfs_j):
         """Per read: list of (position, nucleotide mask) imputed for its ambiguous entries at
         the chosen node (column 4 of placement_stats.tsv): wepp_imputed_mutations."""
@@ -707,3 +756,10 @@ def epp_resolve_last_timing():
     d = [ctypes.c_double() for _ in range(4)]
     check(lib.wepp_epp_resolve_last_timing(*[ctypes.byref(x) for x in d]))
     return dict(mark_ms=d[0].value, tables_ms=d[1].value, assign_ms=d[2].value, tally_ms=d[3].value)
+
+
+def epp_neighbors_last_timing():
+    """Device time by phase (ms, summed over the passes) of this thread's last Mat.epp_neighbors / epp_distances call."""
+    d = [ctypes.c_double() for _ in range(3)]
+    check(lib.wepp_epp_neighbors_last_timing(*[ctypes.byref(x) for x in d]))
+    return dict(tables_ms=d[0].value, field_ms=d[1].value, region_ms=d[2].value)

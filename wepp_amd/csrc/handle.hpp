@@ -80,6 +80,11 @@ struct wepp_mat {
         std::vector<std::pair<void*, size_t>> blocks;
         ~DevBlockCache() { for (auto& b : blocks) (void)hipFree(b.first); }
     } epp_cache;
+    // wepp_epp_neighbors (neighbors_capi.cpp): one past the last pre-order index of every subtree, derived from
+    // parent_dfs and uploaded by the first call (in `allocs`); columns per pass forced by WEPP_NBR_PASS_COLS
+    // (-1: not read yet, 0: sized by the memory budget)
+    const uint32_t* nbr_dfs_end = nullptr;
+    int nbr_pass_cols = -1;
     std::vector<uint32_t> epp_pending;   // EPP lists of the last wepp_epp_map that did not fit the caller's buffer (wepp_epp_fetch_lists)
     std::vector<void*> allocs;
     uint32_t tile_reads = 64;

@@ -2,6 +2,7 @@
 // wepp_filter::cartesian_map, on files: MAT .pb[.gz] + reads .pb (sam.proto, as written by
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
 //   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE [--resolve RESIDUAL]]
+//            [--neighbors FILE [--radius R] [--max-neighbors L]]
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
@@ -24,6 +25,14 @@
 //                                          the order of FILE.
 //                                          The reference's row order in both files is that of a concurrent hash map and
 //                                          not defined; here the rows follow RESIDUAL.
+// --neighbors FILE [--radius R] [--max-neighbors L]: FILE names selected haplotypes in the format of --assign.  After
+// the map every selected haplotype is expanded to its neighbours (arena::closest_neighbors, arena.cpp:171-207: the
+// haplotypes within R mutations, default 2, reached through haplotypes within R; the L best, default 500, in the
+// reference's order by score, leaf count and identifier -- config.hpp:24-25) and the lists are united ("add
+// neighbors", post_filter.hpp:56-64): one round of the Freyja loop between two runs of --assign.
+//         <outdir>/haplotype_neighbors.csv one row per selected haplotype, in the order of FILE: id,id:distance,... --
+//                                          its neighbours (itself among them) in rank order with their distances.
+//         <outdir>/next_selection.txt      the union in rank order, one identifier per line: the next FILE.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -34,8 +43,8 @@
 #include "wepp_filter.hpp"
 
 int main(int argc, char** argv) {
-    std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, outdir = ".";
-    int device = 0;
+    std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, neighbors_f, outdir = ".";
+    int device = 0, radius = 2, max_neighbors = 500;       // config.hpp:24-25
     bool dump = false;
     for (int i = 1; i < argc; i++) {
         auto need = [&](const char* flag) -> const char* {
@@ -51,14 +60,21 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--dump")) dump = true;
         else if (!strcmp(argv[i], "--assign")) assign_f = need("--assign");
         else if (!strcmp(argv[i], "--resolve")) resolve_f = need("--resolve");
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]]\n"); return 1; }
+        else if (!strcmp(argv[i], "--neighbors")) neighbors_f = need("--neighbors");
+        else if (!strcmp(argv[i], "--radius")) radius = atoi(need("--radius"));
+        else if (!strcmp(argv[i], "--max-neighbors")) max_neighbors = atoi(need("--max-neighbors"));
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]]\n");
         return 1;
     }
     if (!resolve_f.empty() && assign_f.empty()) {
         fprintf(stderr, "ERROR: --resolve needs --assign: residual mutations are attributed to the selected haplotypes\n");
+        return 1;
+    }
+    if (radius < 0 || max_neighbors < 1) {
+        fprintf(stderr, "ERROR: --radius must be at least 0 and --max-neighbors at least 1\n");
         return 1;
     }
     try {
@@ -87,12 +103,10 @@ int main(int argc, char** argv) {
                 printf("node %s %s\n", n->identifier.c_str(), n->parent ? n->parent->identifier.c_str() : "-");
             return 0;
         }
-        // the selection is checked before the device is touched
-        std::vector<MAT::Node*> selected;
-        std::vector<std::string> selected_ids;
-        if (!assign_f.empty()) {
-            std::ifstream in(assign_f);
-            if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", assign_f.c_str()); return 1; }
+        // the selections are checked before the device is touched
+        auto read_selection = [&](const std::string& file, std::vector<MAT::Node*>& nodes, std::vector<std::string>& ids) -> bool {
+            std::ifstream in(file);
+            if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", file.c_str()); return false; }
             std::unordered_set<std::string> seen;
             std::string line;
             while (std::getline(in, line)) {
@@ -100,13 +114,18 @@ int main(int argc, char** argv) {
                 line = line.substr(0, line.find_first_of("\t,"));
                 if (line.empty()) continue;
                 MAT::Node* n = condensed.get_node(line);
-                if (!n) { fprintf(stderr, "ERROR: %s: %s is not a haplotype of the condensed tree\n", assign_f.c_str(), line.c_str()); return 1; }
-                if (!seen.insert(line).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", assign_f.c_str(), line.c_str()); return 1; }
-                selected.push_back(n);
-                selected_ids.push_back(line);
+                if (!n) { fprintf(stderr, "ERROR: %s: %s is not a haplotype of the condensed tree\n", file.c_str(), line.c_str()); return false; }
+                if (!seen.insert(line).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", file.c_str(), line.c_str()); return false; }
+                nodes.push_back(n);
+                ids.push_back(line);
             }
-            if (selected.empty()) { fprintf(stderr, "ERROR: %s names no haplotype\n", assign_f.c_str()); return 1; }
-        }
+            if (nodes.empty()) { fprintf(stderr, "ERROR: %s names no haplotype\n", file.c_str()); return false; }
+            return true;
+        };
+        std::vector<MAT::Node*> selected, pivots;
+        std::vector<std::string> selected_ids, pivot_ids;
+        if (!assign_f.empty() && !read_selection(assign_f, selected, selected_ids)) return 1;
+        if (!neighbors_f.empty() && !read_selection(neighbors_f, pivots, pivot_ids)) return 1;
         // so is the residual list
         std::vector<residual_mutation> residual;
         if (!resolve_f.empty()) residual = load_residual_mutations(resolve_f, reference);
@@ -170,6 +189,24 @@ int main(int argc, char** argv) {
                 for (int k : rr.best[m]) row += "," + selected_ids[(size_t)k];       // arena.cpp:895-903
                 fprintf(f, "%s\n", row.c_str());
             }
+            fclose(f);
+        }
+        if (!pivots.empty()) {
+            std::vector<haplotype_key> keys = haplotype_keys(res, haplotype_leaf_counts(res.haplotypes, mappings));
+            neighbors_result nb;
+            if (closest_neighbors(condensed, pivots, keys, radius, max_neighbors, nb, device) != 0) return 1;
+            f = fopen((outdir + "/haplotype_neighbors.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t k = 0; k < pivots.size(); k++) {
+                std::string row = pivot_ids[k];
+                for (size_t j = 0; j < nb.neighbors[k].size(); j++)
+                    row += "," + keys[(size_t)nb.neighbors[k][j]].id + ":" + std::to_string(nb.distance[k][j]);
+                fprintf(f, "%s\n", row.c_str());
+            }
+            fclose(f);
+            f = fopen((outdir + "/next_selection.txt").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (int h : nb.next_selection) fprintf(f, "%s\n", keys[(size_t)h].id.c_str());
             fclose(f);
         }
     } catch (const std::exception& e) {

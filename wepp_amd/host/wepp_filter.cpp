@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <iterator>
@@ -406,5 +407,75 @@ int resolve_unaccounted_mutations(MAT::Tree& condensed, const std::vector<raw_re
         for (size_t k = 0; k < K; k++)
             if ((best_mask[m * KW + k / 32] >> (k & 31)) & 1u) out.best[m].push_back((int)k);
     }
+    return 0;
+}
+
+std::vector<size_t> haplotype_leaf_counts(const std::vector<MAT::Node*>& haplotypes,
+                                          const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings) {
+    std::vector<size_t> leaves(haplotypes.size(), 0);
+    std::vector<MAT::Node*> remaining;
+    for (size_t k = 0; k < haplotypes.size(); k++) {
+        auto it = node_mappings.find(haplotypes[k]);
+        if (it == node_mappings.end() || it->second.empty()) continue;
+        remaining.assign(1, it->second.front());
+        while (!remaining.empty()) {
+            MAT::Node* curr = remaining.back();
+            remaining.pop_back();
+            if (curr->children.empty()) leaves[k]++;
+            else remaining.insert(remaining.end(), curr->children.begin(), curr->children.end());
+        }
+    }
+    return leaves;
+}
+
+std::vector<haplotype_key> haplotype_keys(const cartesian_map_result& map, const std::vector<size_t>& leaf_count) {
+    std::vector<haplotype_key> keys(map.haplotypes.size());
+    for (size_t k = 0; k < keys.size(); k++)
+        keys[k] = haplotype_key{map.score[k] * std::sqrt(map.dist_divergence[k]), leaf_count[k], map.haplotypes[k]->identifier};
+    return keys;
+}
+
+int closest_neighbors(MAT::Tree& condensed, const std::vector<MAT::Node*>& selected, const std::vector<haplotype_key>& keys,
+                      int max_radius, int num_limit, neighbors_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    const size_t K = selected.size();
+    std::vector<uint32_t> piv;
+    if (arena_indices(mat, bfs, selected, piv) != 0) {
+        wepp_mat_destroy(mat);
+        return 1;
+    }
+    if (keys.size() != bfs.size() || max_radius < 0) {
+        fprintf(stderr, "ERROR: closest_neighbors: %zu keys for %zu haplotypes, radius %d\n", keys.size(), bfs.size(), max_radius);
+        wepp_mat_destroy(mat);
+        return 1;
+    }
+    std::vector<uint64_t> off(K + 1, 0);
+    std::vector<uint32_t> node(std::max<size_t>(K, 1) * 64);
+    std::vector<int32_t> dist(node.size());
+    wepp_neighbors_out o{off.data(), node.data(), dist.data(), node.size(), nullptr, nullptr};
+    int rc = wepp_epp_neighbors(mat, (uint32_t)K, piv.data(), (uint32_t)max_radius, WEPP_NBR_TO_PIVOT, nullptr, &o);
+    if (rc == WEPP_ELIMIT && off[K] > node.size()) {
+        // the guess was short: the sizes are known now
+        node.assign((size_t)off[K], 0);
+        dist.assign((size_t)off[K], 0);
+        o.nbr_node = node.data(); o.nbr_dist = dist.data(); o.nbr_capacity = node.size();
+        rc = wepp_epp_neighbors(mat, (uint32_t)K, piv.data(), (uint32_t)max_radius, WEPP_NBR_TO_PIVOT, nullptr, &o);
+    }
+    if (rc != WEPP_OK) fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+    wepp_mat_destroy(mat);
+    if (rc != WEPP_OK) return 1;
+    out.neighbors.assign(K, {});
+    out.distance.assign(K, {});
+    std::unordered_map<int, int> dist_of;
+    for (size_t k = 0; k < K; k++) {
+        std::vector<int> region(node.begin() + (long)off[k], node.begin() + (long)off[k + 1]);
+        dist_of.clear();
+        for (uint64_t j = off[k]; j < off[k + 1]; j++) dist_of[(int)node[(size_t)j]] = dist[(size_t)j];
+        out.neighbors[k] = rank_neighbors(region, keys, num_limit);
+        for (int h : out.neighbors[k]) out.distance[k].push_back(dist_of[h]);
+    }
+    out.next_selection = add_neighbors(out.neighbors, keys);
     return 0;
 }

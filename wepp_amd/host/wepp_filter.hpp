@@ -1,8 +1,9 @@
 // wepp_filter.hpp -- host-side mirror of the slice of WEPP's own interface that feeds and
 // consumes wepp_filter::cartesian_map (/root/reference/src/WEPP/): raw_read, the reads .pb
 // loader, read masking, the condensed tree, the call itself on top of wepp_epp_map, the
-// read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign, and
-// arena::resolve_unaccounted_mutations on top of wepp_epp_resolve.
+// read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign,
+// arena::resolve_unaccounted_mutations on top of wepp_epp_resolve, and arena::closest_neighbors with the
+// "add neighbors" step of post_filter::iterative_filter on top of wepp_epp_neighbors.
 // Same names and argument meaning as the reference; errors throw MAT::mat_error.
 #pragma once
 #include <array>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "mat.hpp"
+#include "neighbor_rank.hpp"
 #include "residual_file.hpp"
 
 static constexpr int NUM_RANGE_BINS = 50;          // src/WEPP/config.hpp:13
@@ -95,3 +97,23 @@ struct resolve_result {
 int resolve_unaccounted_mutations(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
                                   const std::vector<MAT::Node*>& selected, const std::vector<residual_mutation>& residual,
                                   resolve_result& out, int device = 0);
+
+// haplotype::leaf_count (arena.cpp:16, get_num_leaves, util.cpp:298-316) of every haplotype of `haplotypes`: the
+// leaves of the uncondensed tree below the first node its condensed node stands for
+std::vector<size_t> haplotype_leaf_counts(const std::vector<MAT::Node*>& haplotypes,
+                                          const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings);
+// what score_comparator reads, per haplotype of a finished map (arena order): full_score, leaf_count, identifier
+std::vector<haplotype_key> haplotype_keys(const cartesian_map_result& map, const std::vector<size_t>& leaf_count);
+
+// arena::closest_neighbors (arena.cpp:171-207) for every haplotype of `selected` in one device call: all haplotypes
+// within max_radius mutations of it (node->mutation_distance(target)) that are reached through haplotypes within the
+// radius, the num_limit best of them in score_comparator's order -- arena indices, i.e. indices into `keys` -- with
+// their distances; next_selection: the union over the selection in the same order (post_filter.hpp:56-64)
+struct neighbors_result {
+    std::vector<std::vector<int>> neighbors, distance;            // per selected haplotype, rank order
+    std::vector<int> next_selection;
+};
+// `selected`: nodes of `condensed`, distinct; `keys`: haplotype_keys of the map over `condensed`.  Returns 0, or 1
+// after printing the error.
+int closest_neighbors(MAT::Tree& condensed, const std::vector<MAT::Node*>& selected, const std::vector<haplotype_key>& keys,
+                      int max_radius, int num_limit, neighbors_result& out, int device = 0);
