@@ -168,10 +168,11 @@ __device__ __forceinline__ void emit_result(const DevMAT& m, uint32_t r, const u
 // -----------------------------------------------------------------------------
 constexpr uint32_t WW_R = WAVE_WALK_MAX_EVENTS / 64;      // rows of 64 entries of the largest read: entries per lane
 constexpr int PK_BIAS = 2;
-// LDS of a block of `waves` waves (words): the per-entry partials of the pair pass, one unit = (row of 64 entries, slice of
-// the broadcasts), five words a lane; behind them four words per wave for the block's combination of its waves' bests
-constexpr uint32_t WW_UNITS_MAX = 6, WW_UNIT_WORDS = 5 * 64;
-__host__ __device__ constexpr uint32_t ww_lds_words(uint32_t waves) { return WW_UNITS_MAX * WW_UNIT_WORDS + 4 * waves; }
+// LDS of a block of `waves` waves (words), for a read of more than 64 events (sorted_build below): the two sorted key
+// arrays (64 bits a key), the entries' packed adjustments, their two prefix arrays in sorted order; behind them four
+// words per wave for the block's combination of its waves' bests
+constexpr uint32_t WW_SORT_WORDS = 7 * WAVE_WALK_MAX_EVENTS;
+__host__ __device__ constexpr uint32_t ww_lds_words(uint32_t waves) { return WW_SORT_WORDS + 4 * waves; }
 
 struct Cand {
     int bs;
@@ -264,26 +265,134 @@ __device__ __forceinline__ uint32_t pack_adjust(const IxEnt& ent, uint32_t sw) {
     return (uint32_t)(d + PK_BIAS) | (uint32_t)(adj + PK_BIAS) << 8 | (uint32_t)(dcom + PK_BIAS) << 16 | 1u << 24;
 }
 
-// What the pair pass accumulates for one entry.  Every field is associative and commutative -- cb, cB and T are sums,
-// stopA and stopB minima, fl an OR -- so the broadcasts of a read may be cut into slices that different waves take, and
-// the partials joined in any order: the result is the same, bit for bit.
+// What a sequential walk would know at every entry (n, e) of a read.  Subtrees nest, so:
+//   cb  = the deltas of the entries whose subtree holds n strictly inside (nl < n < el);
+//   T   = the packed sum over the entries of the same node (the lowest of them owns the node and its stretches);
+//   the stretch of untouched descendants starts at n + 1 with c_S = cb + the node's own deltas and stops at the first
+//   entry node or subtree end at or behind n + 1 (its own end at the latest: a leaf's stretch is empty): stopA nodes on;
+//   the stretch behind the subtree starts at e with cB = the deltas of the subtrees that hold e strictly inside and
+//   stops at the first entry node at or behind e, or subtree end behind e (stopB, in half nodes; >= 0x80000000: no
+//   cut); of the entries that end at e the lowest owns it.
+//   "Lower" compares the entries' indices in the read.
 struct PairAcc {
     int cb, cB;
     uint32_t T, stopA, stopB, fl;      // fl bit 0: an entry of the same node with a lower index; bit 1: ... of the same subtree end
 };
-__device__ __forceinline__ void pair_join(PairAcc& a, const PairAcc& b) {
-    a.cb += b.cb; a.cB += b.cB; a.T += b.T;
-    a.stopA = min(a.stopA, b.stopA); a.stopB = min(a.stopB, b.stopB);
-    a.fl |= b.fl;
+
+// ---- a read of more than 64 events: sort and scan instead of all pairs ----
+// Every field of PairAcc is a rank, a prefix sum or a successor query over the entries' node and end keys:
+//   sum of dl over nl < x < el  =  sum of dl over nl < x  -  sum of dl over el <= x      (el <= x implies nl < x),
+// so the workgroup sorts the keys (node, index) and (end, index) -- 64 bits: keys reach 2^25, the index breaks ties, and
+// the lowest index of a run of equal keys is the run's first element; a padding entry has the key NONE and sorts behind
+// every real one --, scans the deltas and the packed adjustments in both orders, and every entry asks six binary
+// searches.  O(E log^2 E) compare-exchanges over the workgroup instead of E^2 pair evaluations on one wave.  Barriers and
+// LDS only: tests/cxx runs this code lane by lane on the CPU.
+// sorted_build: `key` holds (node << 8 | i) at i and (end << 8 | i) at N + i, `pk` the packed adjustments at i (0 for a
+// padding entry), written by the caller; all T threads of the workgroup call it.  Leaves both halves of `key` sorted,
+// ppk[p] = the wrapping sum of pk over the first p + 1 entries in node order, and pdl[p] = the sums of (dl + PK_BIAS)
+// over the first p + 1 entries in node order (low half) and in end order (high half; at most 4 * 256 each).
+template <uint32_t N, uint32_t T>
+__device__ __forceinline__ void sorted_build(unsigned long long* key, const uint32_t* pk, uint32_t* ppk, uint32_t* pdl, uint32_t tid) {
+    static_assert(N <= 256 && (N & (N - 1u)) == 0u, "the index is the low byte of a key; a bitonic network");
+    constexpr uint32_t C = (N + T - 1u) / T;
+    __syncthreads();
+    // (the loops stay rolled: unrolled, the per-stage indices of all stages are hoisted and cost k_step 18 VGPRs)
+#pragma unroll 1
+    for (uint32_t k = 2; k <= N; k <<= 1)
+#pragma unroll 1
+        for (uint32_t j = k >> 1; j; j >>= 1) {
+            // (compare-exchange q of the N of a stage: N / 2 in each half, partners differ in bit j, direction by bit k inside the half)
+            for (uint32_t q = tid; q < N; q += T) {
+                const uint32_t i = ((q & ~(j - 1u)) << 1) | (q & (j - 1u)), l = i | j;
+                const unsigned long long a = key[i], b = key[l];
+                if ((a > b) == (((i & (N - 1u)) & k) == 0u)) { key[i] = b; key[l] = a; }
+            }
+            __syncthreads();
+        }
+    for (uint32_t p = tid; p < N; p += T) {
+        const unsigned long long ka = key[p], kb = key[N + p];
+        const uint32_t pa = (uint32_t)(ka >> 8) != NONE ? pk[ka & 0xFFu] : 0u, pb = (uint32_t)(kb >> 8) != NONE ? pk[kb & 0xFFu] & 0xFFu : 0u;
+        ppk[p] = pa;
+        pdl[p] = (pa & 0xFFu) | pb << 16;
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (uint32_t d = 1; d < N; d <<= 1) {
+        uint32_t x[C], y[C];
+#pragma unroll
+        for (uint32_t c = 0; c < C; c++) {
+            const uint32_t p = tid + c * T;
+            x[c] = y[c] = 0u;
+            if (p < N && p >= d) { x[c] = ppk[p - d]; y[c] = pdl[p - d]; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t c = 0; c < C; c++) {
+            const uint32_t p = tid + c * T;
+            if (p < N && p >= d) { ppk[p] += x[c]; pdl[p] += y[c]; }
+        }
+        __syncthreads();
+    }
+}
+// the rows of a read of R rows into `lds` (7 * 64 R words: 2 N keys, then pk, ppk, pdl), wave r % W of the W its row r, and
+// sorted_build by all of them
+template <uint32_t R, uint32_t W>
+__device__ __forceinline__ void sorted_fill(uint32_t* lds, uint32_t lane, uint32_t wv, const uint32_t (&bnode)[R], const uint32_t (&bend)[R], const uint32_t (&bpk)[R]) {
+    constexpr uint32_t N = 64 * R;
+    unsigned long long* key = (unsigned long long*)lds;
+    uint32_t* pk = lds + 4 * N;
+#pragma unroll
+    for (uint32_t r = 0; r < R; r++)
+        if (r % W == wv) {
+            const uint32_t i = lane + 64 * r;
+            key[i] = (unsigned long long)bnode[r] << 8 | i;
+            key[N + i] = (unsigned long long)bend[r] << 8 | i;
+            pk[i] = bpk[r];
+        }
+    sorted_build<N, 64 * W>(key, pk, pk + N, pk + 2 * N, wv * 64 + lane);
+}
+// entry i = (node, end) of the read against what sorted_fill left in `lds`
+template <uint32_t N>
+__device__ __forceinline__ PairAcc sorted_query(const uint32_t* lds, uint32_t i, uint32_t node, uint32_t end) {
+    const unsigned long long* key = (const unsigned long long*)lds;
+    const uint32_t *ppk = lds + 5 * N, *pdl = lds + 6 * N;
+    PairAcc a{0, 0, 0u, NONE, NONE, 0u};
+    if (node == NONE) return a;
+    // how many keys lie below x: node keys < n, <= n, end keys <= n; then node keys < e, end keys <= e, < e -- three searches in
+    // step at a time (six in step cost the walkers of k_step a resident wave per SIMD in registers)
+    const unsigned long long n0 = (unsigned long long)node << 8, e0 = (unsigned long long)end << 8;
+    const unsigned long long x[6] = {n0, n0 + 256u, n0 + 256u, e0, e0 + 256u, e0};
+    const uint32_t half[6] = {0u, 0u, N, 0u, N, N};
+    uint32_t r[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t g = 0; g < 6; g += 3) {
+#pragma unroll
+        for (uint32_t s = N / 2; s; s >>= 1)
+#pragma unroll
+            for (uint32_t q = g; q < g + 3; q++) if (key[half[q] + r[q] + s - 1u] < x[q]) r[q] += s;
+#pragma unroll
+        for (uint32_t q = g; q < g + 3; q++) if (key[half[q] + r[q]] < x[q]) r[q]++;
+    }
+    auto dl_node = [&](uint32_t c) { return c ? (int)(pdl[c - 1u] & 0xFFFFu) - PK_BIAS * (int)c : 0; };
+    auto dl_end = [&](uint32_t c) { return c ? (int)(pdl[c - 1u] >> 16) - PK_BIAS * (int)c : 0; };
+    auto key_at = [&](uint32_t h, uint32_t c) { return c < N ? (uint32_t)(key[h + c] >> 8) : NONE; };
+    a.cb = dl_node(r[0]) - dl_end(r[2]);
+    a.cB = dl_node(r[3]) - dl_end(r[4]);
+    a.T = (r[1] ? ppk[r[1] - 1u] : 0u) - (r[0] ? ppk[r[0] - 1u] : 0u);
+    // (the entry itself is in both runs: r[0], r[5] < N)
+    a.fl = ((uint32_t)(key[r[0]] & 0xFFu) != i ? 1u : 0u) | ((uint32_t)(key[N + r[5]] & 0xFFu) != i ? 2u : 0u);
+    a.stopA = min(key_at(0u, r[1]), key_at(N, r[2])) - (node + 1u);
+    const uint32_t na = key_at(0u, r[3]), eb = key_at(N, r[4]);      // (entry nodes at e cut, ends behind e cut)
+    a.stopB = min(na != NONE ? (na - end) << 1 : NONE, eb != NONE ? ((eb - end) << 1) - 1u : NONE);
+    return a;
 }
 
-// The work of ONE wave of a workgroup of W waves on one read of E <= 64 R entries.  The wave holds all entries for the
-// broadcasts (lane + 64 r).  The pair pass is cut into units = (row of 64 entries, slice of the broadcasts): a read of
-// `rows` rows takes P slices so that every wave of the workgroup has pairs to score -- the pass is the time of such a
-// read, ~20 instructions a pair on a single wave --, wave u % W takes unit u, and the partials of a row meet in LDS
-// (`part`, ww_lds_words) where wave row % W joins them, scores the row's nodes and asks for their stretches.
+// The work of ONE wave of a workgroup of W waves on one read of E <= 64 R entries: row r = the entries lane + 64 r.  A
+// read of one row is a wave's own (R == 1): an all-pairs pass of register broadcasts.  A larger read is the
+// workgroup's: wave r % W puts row r into LDS (`lds`, ww_lds_words), all waves sort and scan (sorted_build), then wave
+// r % W asks for the entries of row r, scores their nodes and asks for their stretches.
 template <uint32_t R, uint32_t W>
-__device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, uint32_t lane, uint32_t wv, const ReadLists& L, uint32_t* part, Cand& best,
+__device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, uint32_t lane, uint32_t wv, const ReadLists& L, uint32_t* lds, Cand& best,
                                           uint32_t& bytes, uint32_t& wave_bytes) {
     constexpr uint32_t OWN = (R + W - 1) / W;      // rows a wave finishes
     const uint32_t E = L.E;
@@ -310,45 +419,28 @@ __device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, u
             }
         }
     }
-    const uint32_t rows = max((E + 63) / 64, 1u);
-    const uint32_t P = R == 1 ? 1u : W >= 2 * rows ? W / rows : (rows % W ? 2u : 1u);
-    const uint32_t H = (E + P - 1) / P;            // broadcasts of a slice
-    // ---- all pairs: what a sequential walk would know at every entry.  Subtrees nest, so for entry (n, e):
-    //   cb  = the deltas of the entries whose subtree holds n strictly inside (nl < n < el);
-    //   T   = the packed sum over the entries of the same node (the lowest of them owns the node and its stretches);
-    //   the stretch of untouched descendants starts at n + 1 with c_S = cb + the node's own deltas and stops at the first
-    //   entry node or subtree end at or behind n + 1 (its own end at the latest: a leaf's stretch is empty);
-    //   the stretch behind the subtree starts at e with cB = the deltas of the subtrees that hold e strictly inside and
-    //   stops at the first entry node at or behind e, or subtree end behind e; of the entries that end at e the lowest
-    //   owns it.  Differences wrap to huge values when the cut lies in front of the start, so plain minima do.
-    //   "Lower" compares the entries' indices in the read, whatever slice a broadcast comes from.
-    auto pass = [&](uint32_t row, uint32_t s0, uint32_t s1) -> PairAcc {
-        uint32_t node = NONE, end = NONE;
-#pragma unroll
-        for (uint32_t r = 0; r < R; r++) if (r == row) { node = bnode[r]; end = bend[r]; }
+    // ---- all pairs (R == 1): differences wrap to huge values when the cut lies in front of the start, so plain minima do
+    auto pairs = [&]() -> PairAcc {
+        const uint32_t node = bnode[0], end = bend[0];
         PairAcc a{0, 0, 0u, NONE, NONE, 0u};
         unsigned long long lower_same = 0ull, lower_end = 0ull;
-        const uint32_t mg = row * 64 + lane, sA = node + 1u, e2 = end << 1;
-#pragma unroll
-        for (uint32_t rl = 0; rl < R; rl++) {
-            const uint32_t lo = s0 > 64 * rl ? s0 - 64 * rl : 0u, hi = s1 > 64 * rl ? min(64u, s1 - 64 * rl) : 0u;
-            for (uint32_t ll = lo; ll < hi; ll++) {
-                const uint32_t nl = (uint32_t)__builtin_amdgcn_readlane((int)bnode[rl], (int)ll), el = (uint32_t)__builtin_amdgcn_readlane((int)bend[rl], (int)ll);
-                const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)bpk[rl], (int)ll);
-                const int dl = (int)(pl & 0xFFu) - PK_BIAS;
-                const uint32_t g = rl * 64 + ll, nl1 = nl + 1u, span = el - nl1, nl2 = nl << 1, el2 = (el << 1) - 1u;
-                const unsigned long long lower = __ballot(g < mg);
-                if (dl != 0) {
-                    if (node - nl1 < span) a.cb += dl;
-                    if (end - nl1 < span) a.cB += dl;
-                }
-                const bool same = nl == node;
-                a.T += same ? pl : 0u;
-                lower_same |= __ballot(same) & lower;
-                lower_end |= __ballot(el == end) & lower;
-                a.stopA = min(a.stopA, min(nl - sA, el - sA));
-                a.stopB = min(a.stopB, min(nl2 - e2, el2 - e2));       // (entry nodes at e cut, ends behind e cut)
+        const uint32_t sA = node + 1u, e2 = end << 1;
+        for (uint32_t ll = 0; ll < E; ll++) {
+            const uint32_t nl = (uint32_t)__builtin_amdgcn_readlane((int)bnode[0], (int)ll), el = (uint32_t)__builtin_amdgcn_readlane((int)bend[0], (int)ll);
+            const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)bpk[0], (int)ll);
+            const int dl = (int)(pl & 0xFFu) - PK_BIAS;
+            const uint32_t nl1 = nl + 1u, span = el - nl1, nl2 = nl << 1, el2 = (el << 1) - 1u;
+            const unsigned long long lower = __ballot(ll < lane);
+            if (dl != 0) {
+                if (node - nl1 < span) a.cb += dl;
+                if (end - nl1 < span) a.cB += dl;
             }
+            const bool same = nl == node;
+            a.T += same ? pl : 0u;
+            lower_same |= __ballot(same) & lower;
+            lower_end |= __ballot(el == end) & lower;
+            a.stopA = min(a.stopA, min(nl - sA, el - sA));
+            a.stopB = min(a.stopB, min(nl2 - e2, el2 - e2));       // (entry nodes at e cut, ends behind e cut)
         }
         a.fl = (uint32_t)((lower_same >> lane) & 1ull) | (uint32_t)((lower_end >> lane) & 1ull) << 1;
         return a;
@@ -391,29 +483,21 @@ __device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, u
         // (the read's offsets, words, list heads and stream record once; a 32-byte index entry per list entry)
         wave_bytes += (row == 0 ? 8 + 12 * L.k + 80 + 16 : 0) + 32 * min(64u, E - 64 * row);
     };
-    if (R == 1) {
-        finish(0u, pass(0u, 0u, E), obase[0], orank[0], onst[0]);
-        return;
-    }
-    for (uint32_t u = wv; u < rows * P; u += W) {
-        const uint32_t row = u / P, p = u - row * P;
-        const PairAcc a = pass(row, p * H, min(E, (p + 1) * H));
-        uint32_t* o = part + u * WW_UNIT_WORDS + lane;
-        // (|cb|, |cB| <= 2 * 256: sixteen bits each)
-        o[0] = ((uint32_t)a.cb & 0xFFFFu) | (uint32_t)a.cB << 16; o[64] = a.T; o[128] = a.stopA; o[192] = a.stopB; o[256] = a.fl;
-    }
-    __syncthreads();
+    if constexpr (R == 1) {
+        finish(0u, pairs(), obase[0], orank[0], onst[0]);
+    } else {
+        constexpr uint32_t N = 64 * R;
+        sorted_fill<R, W>(lds, lane, wv, bnode, bend, bpk);
+        const uint32_t rows = max((E + 63) / 64, 1u);
 #pragma unroll
-    for (uint32_t j = 0; j < OWN; j++) {
-        const uint32_t row = wv + j * W;
-        if (row >= rows) break;
-        PairAcc a{0, 0, 0u, NONE, NONE, 0u};
-        for (uint32_t p = 0; p < P; p++) {
-            const uint32_t* o = part + (row * P + p) * WW_UNIT_WORDS + lane;
-            const uint32_t cc = o[0];
-            pair_join(a, PairAcc{(int)(int16_t)(cc & 0xFFFFu), (int)cc >> 16, o[64], o[128], o[192], o[256]});
+        for (uint32_t j = 0; j < OWN; j++) {
+            const uint32_t row = wv + j * W;
+            if (row >= rows) break;
+            uint32_t node = NONE, end = NONE;
+#pragma unroll
+            for (uint32_t r = 0; r < R; r++) if (r == row) { node = bnode[r]; end = bend[r]; }
+            finish(row, sorted_query<N>(lds, lane + 64 * row, node, end), obase[j], orank[j], onst[j]);
         }
-        finish(row, a, obase[j], orank[j], onst[j]);
     }
 }
 
@@ -428,9 +512,8 @@ __device__ __forceinline__ void wave_walk_body(const DevMAT& m, uint32_t* lds, u
                                                int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
                                                uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
                                                const uint32_t* __restrict__ wsid) {
-    static_assert(W == 2 || W == 4, "the slices of wave_read are laid out for two or four waves");
-    static_assert(WW_R == 4 && WW_UNITS_MAX == 6, "the largest read has four rows: at most six units (three rows, two slices)");
-    uint32_t* part_w = lds + WW_UNITS_MAX * WW_UNIT_WORDS;      // [4][W]: score, total, rank, has_unique of every wave
+    static_assert(7 * 64 * WW_R == WW_SORT_WORDS, "wave_read lays the sorted pass of the largest read out in WW_SORT_WORDS");
+    uint32_t* part_w = lds + WW_SORT_WORDS;                    // [4][W]: score, total, rank, has_unique of every wave
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const DevWalk ix = m.walks[WC_SLOT];                 // the walk arena: every stream is a slice of it

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
                 // many events, but few enough for a wave per 64 of them to hold them all (lane = list entry, wave_kernels.hip):
                 // no jobs; the read keeps its chunked class in the diagnostics.  (<= 64: a wave of its own, listed from the
                 // front; more: the four waves of a block, listed from the back.)  Up to direct.ww_max_* of them per routing
-                // block and round -- all or none in practice: the all-pairs pass is the cheaper way for the one read in a
+                // block and round -- all or none in practice: the wave pass is the cheaper way for the one read in a
                 // thousand of a sequencing run, the jobs for a batch FULL of such reads (a star-like tree: 29 000 of a
                 // million -- 0.60 ms a step by waves, 0.36 by jobs), and a call that needs both pays for both; the host
                 // picks from the counts of the handle's previous call (capi.cpp)

@@ -519,7 +519,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl
                                               uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
                                               const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ blind_list,
                                               const uint32_t* __restrict__ blind_count) {
-    extern __shared__ uint32_t lds_all[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_all[];
     walk_body<KW, SD, CHUNKED>(m, pl, jb, sd_rows, blockIdx.x, lds_all, read_off, read_word, root_score, best_bfs_j, score_out, num_best, flags,
                                work_counter, wsid, blind_list, blind_count);
 }
@@ -533,9 +533,11 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl
 // what the counters ask for (a workgroup per read with more than 64 events, a wave per smaller one), rounded up to a
 // multiple of WALK_XCDS so that a walker's XCD is still its own index % 8, at most `wave_cap` (beyond, the wave-role
 // workgroups loop); with wave_cap = 0 (the handle cuts such reads into jobs: the lists are empty) this is the blind
-// k_walk<WALK8_K>.  Both roles live in the walkers' dynamic LDS: the launch asks for what k_walk asks.
+// k_walk<WALK8_K>.  Both roles live in the walkers' dynamic LDS: the launch asks for what k_walk asks.  The LDS leaves
+// the walkers 22 waves a CU; six waves a SIMD is what the registers must leave them (at most 80 VGPRs: the wave role's
+// sorted pass is the widest part, and the compiler is told so that it does not trade a wave for a shorter schedule).
 // -----------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * WALK_WAVES) void k_step(DevMAT m, uint32_t sd_rows, uint32_t wave_cap, uint32_t n_reads,
+__global__ __launch_bounds__(64 * WALK_WAVES) __attribute__((amdgpu_waves_per_eu(6))) void k_step(DevMAT m, uint32_t sd_rows, uint32_t wave_cap, uint32_t n_reads,
                                               const uint32_t* __restrict__ read_off,
                                               const uint32_t* __restrict__ read_word,
                                               const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
@@ -544,7 +546,7 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_step(DevMAT m, uint32_t sd_
                                               const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ wlist,
                                               const uint32_t* __restrict__ wcount, const uint32_t* __restrict__ wwlist,
                                               const uint32_t* __restrict__ wwcount) {
-    extern __shared__ uint32_t lds_all[];
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds_all[];
     uint32_t n_wave = 0, n_small = 0, n_big = 0;
     if (wave_cap) {
         n_small = (uint32_t)__builtin_amdgcn_readfirstlane((int)wwcount[0]);

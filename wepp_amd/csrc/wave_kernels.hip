@@ -7,20 +7,21 @@
 // Here the events of ONE read are spread over the lanes of one wave and nothing is walked:
 //   * every lane loads up to WW_R entries of the read's position lists (an entry = a mutation of a stream node at a
 //     listed position, with the node's subtree end: flatmat.hpp IxEnt) -- coalesced, the lists are contiguous;
-//   * an all-pairs pass over the read's E entries (broadcasts, no memory) gives every entry what a sequential walk
-//     would know on arrival: c_S in front of its node = c_S of an empty path + the deltas of the entries whose subtree
-//     holds the node; the other entries of the same node (a node that mutates several listed positions); and, for the
-//     two stretches of untouched nodes that start behind an entry -- its descendants, from node + 1, and what follows
-//     its subtree, from end --, their c_S, where they stop (the next node, descendant start or subtree end of any
-//     entry) and whether another entry owns the same stretch;
+//   * every entry learns what a sequential walk would know on arrival: c_S in front of its node = c_S of an empty path
+//     + the deltas of the entries whose subtree holds the node; the other entries of the same node (a node that mutates
+//     several listed positions); and, for the two stretches of untouched nodes that start behind an entry -- its
+//     descendants, from node + 1, and what follows its subtree, from end --, their c_S, where they stop (the next node,
+//     descendant start or subtree end of any entry) and whether another entry owns the same stretch.  Up to 64 entries:
+//     an all-pairs pass of register broadcasts on the read's one wave.  More: all of these are ranks, prefix sums and
+//     successors over the entries' node and end keys, so the workgroup sorts both key sets in LDS, scans the deltas in
+//     both orders and every entry asks six binary searches (place_dev.hpp: sorted_build, sorted_query);
 //   * every lane scores its node (the formula of the walk and of the sweep's node-by-node path, usher_mapper.cpp:
 //     191-265, 455-456) and asks the range queries of its stretches (one byte of the sparse table, then four 16-byte
 //     loads: flatmat.hpp), all lanes at once;
 //   * a wave reduction leaves (score, rank, count, has_unique).
 // The device code is in place_dev.hpp (wave_walk_body, wave_read): by default it runs in the first workgroups of k_step
 // (walk_kernels.hip), in one launch with the plain walks; this unit keeps the launch of its own (WEPP_STEP_UNFUSED=1).
-// A read with more than 64 events takes all waves of a workgroup, and the pair pass is cut into units = (row of 64
-// entries, slice of the broadcasts) so that every wave has pairs to score; the partials of a row meet in LDS.
+// A read with more than 64 events takes all waves of a workgroup: they sort together, wave r % W scores row r.
 // A handful of dependent memory round trips per read, whatever its events.  Exact: the same nodes get the same scores
 // as in the sequential walk (tests/walk_model.py is the CPU model of that walk; the GPU parity tests cover this kernel
 // through every batch that holds such reads, and test_reads_with_many_events_vs_oracle aims at it).
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(64 * WW_WAVES) void k_walk_wave(DevMAT m, const uin
                                                                 uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
                                                                 const uint32_t* __restrict__ wsid) {
     static_assert(WAVE_WALK_MAX_EVENTS == 64 * WW_WAVES, "a block holds the largest read");
-    __shared__ uint32_t lds[ww_lds_words(WW_WAVES)];
+    __shared__ __attribute__((aligned(16))) uint32_t lds[ww_lds_words(WW_WAVES)];      // (64-bit sort keys)
     const uint32_t n_small = (uint32_t)__builtin_amdgcn_readfirstlane((int)count[0]), n_big = (uint32_t)__builtin_amdgcn_readfirstlane((int)count[1]);
     wave_walk_body<WW_WAVES>(m, lds, blockIdx.x, gridDim.x, list, n_small, n_big, n_reads, read_off, read_word, root_score, best_bfs_j, score_out, num_best,
                              flags, work_counter, wsid);
