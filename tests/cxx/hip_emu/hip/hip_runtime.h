@@ -1,11 +1,14 @@
 #pragma once
-// A CPU stand-in for the few pieces of the HIP runtime that assign_kernels.hip uses, for tests/test_assign_emulation.py:
-// the kernels are compiled as plain C++ and run with ONE HOST THREAD PER LANE, in lock step at every cross-lane
-// operation (__ballot, __shfl_xor: a barrier per wave; __syncthreads: a barrier per workgroup), one workgroup after the
-// other.  Atomics are the host's.  It checks the kernels' logic and indexing without a GPU; it says nothing about
-// speed, occupancy or the memory model of the device.
+// A CPU stand-in for the pieces of HIP that the WEPP entry points use (tests/epp_emu.py, tests/test_sorted_pass_emulation.py).
+// Kernels are compiled as plain C++ and run with ONE HOST THREAD PER LANE, in lock step at every cross-lane operation
+// (__ballot, __shfl_xor: a barrier per wave; __syncthreads: a barrier per workgroup), one workgroup after the other;
+// atomics are the host's.  The runtime is the host's too: device memory is malloc'ed memory, a copy is a memcpy done at
+// once, streams and events do nothing.  So the host sides of the entry points compile unchanged against it.  It checks
+// logic, indexing, buffer sizes and launch order without a GPU; it says nothing about speed, occupancy, the memory
+// model of the device or asynchrony between streams.
 #include <pthread.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 #include <algorithm>
 #include <thread>
@@ -23,9 +26,41 @@ extern unsigned char g_emu_lds[];
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 struct uint2 { uint32_t x, y; };
 inline uint2 make_uint2(uint32_t a, uint32_t b) { return uint2{a, b}; }
-typedef int hipError_t; typedef void* hipStream_t;
-constexpr int hipSuccess = 0;
+typedef int hipError_t; typedef void* hipStream_t; typedef void* hipEvent_t;
+constexpr int hipSuccess = 0, hipErrorOutOfMemory = 2;
+enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
+constexpr unsigned hipHostMallocPortable = 1, hipEventDisableTiming = 2;
 inline hipError_t hipGetLastError() { return 0; }
+inline const char* hipGetErrorString(hipError_t e) { return e ? "emulated HIP error" : "no error"; }
+inline hipError_t hipSetDevice(int) { return 0; }
+inline hipError_t hipGetDevice(int* d) { *d = 0; return 0; }
+inline hipError_t hipDeviceSynchronize() { return 0; }
+inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
+// a block is filled with EMU_FILL and followed by a guard of the same: a value read before it was written is
+// conspicuous, and a store outside what was asked for can be found afterwards (emu_guard_check, epp_emu.cpp)
+constexpr uint32_t EMU_FILL = 0xDEADBEEFu;
+constexpr size_t EMU_GUARD_BYTES = 64;
+inline hipError_t hipMalloc(void** p, size_t bytes) {
+    const size_t words = (bytes + EMU_GUARD_BYTES + 3) / 4;
+    uint32_t* w = (uint32_t*)malloc(words * 4);
+    if (!w) return hipErrorOutOfMemory;
+    std::fill(w, w + words, EMU_FILL);
+    *p = w;
+    return 0;
+}
+template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { return hipMalloc((void**)p, bytes); }
+inline hipError_t hipFree(void* p) { free(p); return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned = 0) { return (*p = malloc(bytes)) ? 0 : hipErrorOutOfMemory; }
+inline hipError_t hipHostFree(void* p) { free(p); return 0; }
+inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { if (bytes) memcpy(dst, src, bytes); return 0; }
+inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind k, hipStream_t) { return hipMemcpy(dst, src, bytes, k); }
+inline hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t) { if (bytes) memset(dst, v, bytes); return 0; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return 0; }
+inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
+inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
+inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
+inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return 0; }
 extern thread_local dim3 threadIdx, blockIdx;
 extern dim3 blockDim, gridDim;
 using std::min; using std::max;

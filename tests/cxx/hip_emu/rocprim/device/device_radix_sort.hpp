@@ -1,5 +1,5 @@
-// serial stand-in for the rocPRIM primitive resolve_kernels.hip adds to those of assign_kernels.hip (a stable sort of
-// (key, value) pairs by bits [begin_bit, end_bit) of the key); the rest is ../../../hip_emu
+// serial stand-in for the rocPRIM primitive resolve_kernels.hip uses (a stable sort of (key, value) pairs by bits
+// [begin_bit, end_bit) of the key; see ../../hip/hip_runtime.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <numeric>

@@ -1,4 +1,4 @@
-// serial stand-in for the one rocPRIM primitive assign_kernels.hip uses (see ../../hip/hip_runtime.h)
+// serial stand-in for the rocPRIM primitive assign_kernels.hip uses (see ../../hip/hip_runtime.h)
 #pragma once
 #include <hip/hip_runtime.h>
 namespace rocprim {

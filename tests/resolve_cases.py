@@ -51,6 +51,10 @@ def hand_cases():
     big = 2**31 - 1
     case("int64", [[(5, w.A, w.C)], [(5, w.A, w.C)], [(5, w.A, w.C)], []], [1, 1, 1, 1], [30, 30, 30, 30], [big, big, big, big],
          [(5, w.A, w.C), (12, w.A, w.A)])
+    # the touched read that comes last (by index and in window order) ends with an inserted word that decides its ties:
+    # N at 40 puts haplotype 2 (G40T) level with haplotype 1.  The end offset of the touched batch is this word's: one
+    # word less and haplotype 2 drops out of best_mask
+    case("last word", [[], [(5, w.A, w.C)]], [1, 1], [44, 45], [2, 3], [(40, w.G, w.G)], sels=([0, 1, 2, 3], [2, 1]))
     # no read is touched
     case("untouched", [[(5, w.A, w.C)], []], [1, 10], [30, 40], [1, 1], [(5, w.A, w.T), (50, w.A, w.A), (20, w.A, w.C)],
          sels=([0, 1, 2, 3],))

@@ -12,13 +12,11 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 #include <string>
 #include <vector>
 
 #include "epp.hpp"
 #include "epp_host.hpp"
-#include "handle.hpp"
 #include "staged_copy.hpp"
 
 namespace {
@@ -29,67 +27,6 @@ struct EppTiming { float select_ms = 0, sweep1_ms = 0, sweep2_ms = 0, finish_ms 
 thread_local EppTiming g_last;
 
 }  // namespace
-
-namespace wepp {
-
-int epp_validate_reads(const wepp_epp_reads* rd, long long* total_degree_out) {
-    const uint32_t R = rd->n_reads;
-    long long total_degree = 0;
-    for (uint32_t r = 0; r < R; r++) {
-        if (rd->read_off[r + 1] < rd->read_off[r]) return set_error(WEPP_EINVAL, "read_off is not monotone");
-        if (rd->start[r] < 1 || rd->end[r] < rd->start[r] || (uint32_t)rd->end[r] > WEPP_MAX_POSITION)
-            return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": window must satisfy 1 <= start <= end <= 2^20 - 2");
-        if (rd->degree[r] < 0) return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": negative degree");
-        total_degree += rd->degree[r];
-        uint32_t prev = 0;
-        for (uint32_t j = rd->read_off[r]; j < rd->read_off[r + 1]; j++) {
-            const uint32_t w = rd->read_word[j];
-            const uint32_t pos = w & 0xFFFFFu, ref = (w >> 20) & 15u, mut = (w >> 24) & 15u;
-            if (pos == 0 || pos > WEPP_MAX_POSITION || pos <= prev)
-                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": mutations must be sorted by position, unique, in 1..2^20-2");
-            if (mut == ref || mut == 0)
-                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": a listed mutation must differ from the reference base (sam2pb.cpp:521-535)");
-            prev = pos;
-        }
-    }
-    if (total_degree_out) *total_degree_out = total_degree;
-    return WEPP_OK;
-}
-
-// order by (start, end, index).  Window bounds are genome positions: two stable counting passes (end,
-// then start) instead of a comparison sort through two indirections (≈0.1 s per 1 M reads)
-void epp_window_order(const wepp_epp_reads* rd, std::vector<uint32_t>& order) {
-    const uint32_t R = rd->n_reads;
-    order.resize(R);
-    int32_t lo = 0, hi = 0;
-    for (uint32_t r = 0; r < R; r++) {
-        lo = std::min({lo, rd->start[r], rd->end[r]});
-        hi = std::max({hi, rd->start[r], rd->end[r]});
-    }
-    if (lo < 0 || (uint64_t)hi > (1ull << 24)) {          // not positions: the general way
-        std::iota(order.begin(), order.end(), 0u);
-        std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-            if (rd->start[a] != rd->start[b]) return rd->start[a] < rd->start[b];
-            if (rd->end[a] != rd->end[b]) return rd->end[a] < rd->end[b];
-            return a < b;
-        });
-    } else {
-        std::vector<uint32_t> tmp(R), cnt((size_t)hi + 2);
-        auto pass = [&](const int32_t* key, const uint32_t* in, uint32_t* out) {
-            std::fill(cnt.begin(), cnt.end(), 0u);
-            for (uint32_t s = 0; s < R; s++) cnt[(size_t)key[in ? in[s] : s] + 1]++;
-            for (size_t k = 1; k < cnt.size(); k++) cnt[k] += cnt[k - 1];
-            for (uint32_t s = 0; s < R; s++) {
-                const uint32_t r = in ? in[s] : s;
-                out[cnt[(size_t)key[r]]++] = r;
-            }
-        };
-        pass(rd->end, nullptr, tmp.data());
-        pass(rd->start, tmp.data(), order.data());
-    }
-}
-
-}  // namespace wepp
 
 extern "C" int wepp_mat_dfs_order(const wepp_mat_t* mat, uint32_t* ids) {
     if (!mat || !ids) return set_error(WEPP_EINVAL, "null argument");
@@ -187,33 +124,24 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
                                           " bytes of LDS (window bitmap + allele table): reads too long");
 
     // ---- device copies of the reads ------------------------------------------------------
-    DevPool pool(mat);
-    uint32_t *d_off, *d_word, *d_order, *d_wemax;
-    int32_t *d_start, *d_end, *d_degree;
+    DevPool pool(mat->epp_cache);
+    DevReads reads;
+    if (int rc = upload_reads(pool, rd, order, stream, &reads)) return rc;
+    uint32_t* d_wemax;
     EppGroup* d_groups;
-    hipError_t e;
-#define GET(p, n) if ((e = pool.get(&p, (n))) != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    GET(d_off, (size_t)R + 1) GET(d_word, W) GET(d_order, R) GET(d_start, R) GET(d_end, R) GET(d_degree, R)
-    GET(d_groups, G) GET(d_wemax, G)
-    HIP_TRY(hipMemcpyAsync(d_off, rd->read_off, ((size_t)R + 1) * 4, hipMemcpyHostToDevice, stream));
-    if (W) HIP_TRY(hipMemcpyAsync(d_word, rd->read_word, W * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_start, rd->start, (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_end, rd->end, (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_degree, rd->degree, (size_t)R * 4, hipMemcpyHostToDevice, stream));
+    DEV_GET(pool, d_groups, G); DEV_GET(pool, d_wemax, G);
     HIP_TRY(hipMemcpyAsync(d_groups, groups.data(), (size_t)G * sizeof(EppGroup), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_wemax, we_max.data(), (size_t)G * 4, hipMemcpyHostToDevice, stream));
 
-    hipEvent_t ev[5];
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; i++) (void)hipEventDestroy(e[i]); } } evg{ev};
+    DevEvents<5> ev;
+    if (int rc = ev.create()) return rc;
     HIP_TRY(hipEventRecord(ev[0], stream));
 
     // ---- window streams --------------------------------------------------------------------
     const uint64_t E = mat->epp_events;
     const uint32_t nblk = (uint32_t)((E + EPP_SEL_EVENTS - 1) / EPP_SEL_EVENTS);
     uint32_t *d_cnt, *d_totals;
-    GET(d_cnt, (size_t)G * std::max<uint32_t>(nblk, 1)) GET(d_totals, G)
+    DEV_GET(pool, d_cnt, (size_t)G * std::max<uint32_t>(nblk, 1)); DEV_GET(pool, d_totals, G);
     std::vector<uint32_t> totals(G, 0);
     if (nblk) {
         HIP_TRY(launch_epp_select_count(mat->epp_word, E, d_groups, d_wemax, G, nblk, d_cnt, stream));
@@ -245,7 +173,7 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     const uint32_t n_jobs = (uint32_t)n_jobs64;
     HIP_TRY(hipMemcpyAsync(d_groups, groups.data(), (size_t)G * sizeof(EppGroup), hipMemcpyHostToDevice, stream));
     uint32_t *d_stw, *d_stn;
-    GET(d_stw, total_events) GET(d_stn, total_events)
+    DEV_GET(pool, d_stw, total_events); DEV_GET(pool, d_stn, total_events);
     if (nblk) HIP_TRY(launch_epp_select_scatter(mat->epp_word, mat->epp_node, E, d_groups, d_wemax, G, nblk, d_cnt, d_stw, d_stn, stream));
     HIP_TRY(hipEventRecord(ev[1], stream));
 
@@ -254,7 +182,7 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     int32_t *d_pmin, *d_pnet, *d_best;
     uint32_t *d_pcnt, *d_mult;
     long long* d_fx;
-    GET(d_pmin, rows) GET(d_pcnt, rows) GET(d_pnet, rows) GET(d_best, R) GET(d_mult, R) GET(d_fx, R)
+    DEV_GET(pool, d_pmin, rows); DEV_GET(pool, d_pcnt, rows); DEV_GET(pool, d_pnet, rows); DEV_GET(pool, d_best, R); DEV_GET(pool, d_mult, R); DEV_GET(pool, d_fx, R);
     int fx_bits = 62;
     for (long long s = total_degree; s > 0; s >>= 1) fx_bits--;
     fx_bits = std::min(fx_bits, 52);
@@ -263,7 +191,7 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     a.chunk_events = chunk_events; a.bm_words = bm_words; a.tab_rows = tab_rows;
     a.bin_size = genome_size / EPP_BINS;
     a.st_word = d_stw; a.st_node = d_stn;
-    a.read_off = d_off; a.read_word = d_word; a.start = d_start; a.end = d_end; a.degree = d_degree; a.order = d_order;
+    a.read_off = reads.read_off; a.read_word = reads.read_word; a.start = reads.start; a.end = reads.end; a.degree = reads.degree; a.order = reads.order;
     a.part_min = d_pmin; a.part_cnt = d_pcnt; a.part_net = d_pnet;
     a.best = d_best; a.mult = d_mult; a.delta_fx = d_fx;
     a.fx_scale = std::ldexp(1.0, fx_bits);
@@ -301,8 +229,8 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     uint32_t* d_enodes;
     unsigned long long* d_dscore;
     int* d_dcnt = nullptr;
-    GET(d_ebase, R) GET(d_enodes, epp_total) GET(d_dscore, (size_t)N + 1)
-    if (want_cnt) GET(d_dcnt, ((size_t)N + 1) * EPP_BINS)
+    DEV_GET(pool, d_ebase, R); DEV_GET(pool, d_enodes, epp_total); DEV_GET(pool, d_dscore, (size_t)N + 1);
+    if (want_cnt) DEV_GET(pool, d_dcnt, ((size_t)N + 1) * EPP_BINS);
     HIP_TRY(hipMemcpyAsync(d_ebase, epp_base.data(), (size_t)R * 8, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(d_dscore, 0, ((size_t)N + 1) * 8, stream));
     if (want_cnt) HIP_TRY(hipMemsetAsync(d_dcnt, 0, ((size_t)N + 1) * EPP_BINS * 4, stream));
@@ -314,10 +242,10 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
     double *d_score, *d_div = nullptr;
     int *d_counts = nullptr, *d_true = nullptr;
     void* d_scratch;
-    GET(d_score, N)
+    DEV_GET(pool, d_score, N);
     {
         char* sc;
-        GET(sc, epp_finish_scratch_bytes(N))
+        DEV_GET(pool, sc, epp_finish_scratch_bytes(N));
         d_scratch = sc;
     }
     int true_counts[EPP_BINS] = {0};
@@ -325,10 +253,10 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
         // arena::build_range_trees, arena.cpp:137-147
         for (uint32_t r = 0; r < R; r++)
             true_counts[std::min<uint32_t>((uint32_t)rd->start[r] / a.bin_size, EPP_BINS - 1)] += rd->degree[r];
-        GET(d_true, EPP_BINS)
+        DEV_GET(pool, d_true, EPP_BINS);
         HIP_TRY(hipMemcpyAsync(d_true, true_counts, sizeof(true_counts), hipMemcpyHostToDevice, stream));
-        if (out->hap_read_counts) GET(d_counts, (size_t)N * EPP_BINS)
-        if (out->hap_divergence) GET(d_div, N)
+        if (out->hap_read_counts) DEV_GET(pool, d_counts, (size_t)N * EPP_BINS);
+        if (out->hap_divergence) DEV_GET(pool, d_div, N);
     }
     HIP_TRY(launch_epp_finish(N, d_dscore, 1.0 / a.fx_scale, d_score, d_dcnt, d_true, d_counts, d_div, d_scratch, stream));
     HIP_TRY(hipEventRecord(ev[4], stream));
@@ -343,7 +271,6 @@ extern "C" int wepp_epp_map(wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t 
         HIP_TRY(d2h_staged(mat->epp_pending.data(), d_enodes, epp_total * 4, stream));
     } else if (epp_total) HIP_TRY(d2h_staged(out->epp_nodes, d_enodes, epp_total * 4, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-#undef GET
     g_last = EppTiming{};
     (void)hipEventElapsedTime(&g_last.select_ms, ev[0], ev[1]);
     (void)hipEventElapsedTime(&g_last.sweep1_ms, ev[1], ev[2]);

@@ -1,74 +1,99 @@
-// epp_host.hpp -- what the host sides of the WEPP entry points (epp_capi.cpp: wepp_epp_map,
-// assign_capi.cpp: wepp_epp_assign, resolve_capi.cpp: wepp_epp_resolve) share: the per-call device blocks
-// taken from the handle's cache, the validation of a wepp_epp_reads batch, the (start, end) order of its
-// reads, and the argument checks and the genotype table of the entry points that take a selection.
+// epp_host.hpp -- what the host sides of the WEPP entry points (epp_capi.cpp, assign_capi.cpp, resolve_capi.cpp,
+// neighbors_capi.cpp) share, each written once and defined in epp_host.cpp: the per-call device blocks and events, a
+// wepp_epp_reads batch (validation, window order, device copy), the checks and the genotype table of a selection.
+// Nothing here or in assign / resolve / neighbors_capi.cpp knows whether HIP is the device's: tests/epp_emu.py compiles
+// them unchanged against emulated kernels and an emulated runtime (tests/cxx/hip_emu), which tests their logic, buffer
+// sizes and launch order without a GPU -- not speed, occupancy, the device memory model or asynchrony between streams.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstddef>
 #include <cstdint>
-#include <utility>
+#include <string>
 #include <vector>
 
+#include "assign.hpp"
 #include "handle.hpp"
 
 namespace wepp {
 
 struct DevPool {                       // device allocations of one call, taken from / returned to the handle's cache
-    wepp_mat_t* mat;
-    std::vector<std::pair<void*, size_t>> used;
-    explicit DevPool(wepp_mat_t* m) : mat(m) {}
+    wepp_mat::DevBlockCache& cache;
+    std::vector<DevBlock> used;
+    explicit DevPool(wepp_mat::DevBlockCache& c) : cache(c) {}
     ~DevPool() {
-        // (a call that fails half-way may still have kernels in flight on these blocks)
-        (void)hipDeviceSynchronize();
-        for (auto& b : used) mat->epp_cache.blocks.push_back(b);
+        (void)hipDeviceSynchronize();  // (a call that fails half-way may still have kernels in flight on these blocks)
+        for (auto& b : used) cache.blocks.push_back(b);
     }
     template <typename T>
     hipError_t get(T** out, size_t n) {
-        const size_t bytes = (std::max<size_t>(n * sizeof(T), 64) + 255) & ~(size_t)255;
+        const size_t asked = n * sizeof(T), bytes = (std::max<size_t>(asked, 64) + 255) & ~(size_t)255;
         // the smallest cached block that holds the request without wasting more than half of itself
         size_t best = SIZE_MAX;
-        auto& cache = mat->epp_cache.blocks;
-        for (size_t i = 0; i < cache.size(); i++) {
-            const size_t sz = cache[i].second;
-            if (sz >= bytes && sz <= 2 * bytes + (1u << 20) && (best == SIZE_MAX || sz < cache[best].second)) best = i;
+        auto& blocks = cache.blocks;
+        for (size_t i = 0; i < blocks.size(); i++) {
+            const size_t sz = blocks[i].bytes;
+            if (sz >= bytes && sz <= 2 * bytes + (1u << 20) && (best == SIZE_MAX || sz < blocks[best].bytes)) best = i;
         }
         if (best != SIZE_MAX) {
-            used.push_back(cache[best]);
-            cache.erase(cache.begin() + (std::ptrdiff_t)best);
-            *out = (T*)used.back().first;
+            used.push_back(blocks[best]);
+            blocks.erase(blocks.begin() + (std::ptrdiff_t)best);
+            used.back().asked = std::max(used.back().asked, asked);
+            *out = (T*)used.back().ptr;
             return hipSuccess;
         }
         void* p = nullptr;
         hipError_t e = hipMalloc(&p, bytes);
-        if (e != hipSuccess && !cache.empty()) {
+        if (e != hipSuccess && !blocks.empty()) {
             // out of memory with blocks of other sizes parked in the cache: release them and try again
-            for (auto& b : cache) (void)hipFree(b.first);
-            cache.clear();
+            for (auto& b : blocks) (void)hipFree(b.ptr);
+            blocks.clear();
             e = hipMalloc(&p, bytes);
         }
-        if (e == hipSuccess) used.emplace_back(p, bytes);
+        if (e == hipSuccess) used.push_back(DevBlock{p, bytes, asked});
         *out = (T*)p;
         return e;
     }
 };
 
-// the reference's preconditions on a read batch, made explicit (read_off / start / end / degree are non-null
-// when n_reads > 0, read_word when there are words): WEPP_OK, or WEPP_EINVAL with the message set.
-// *total_degree receives the sum of the degrees.
+#define DEV_GET(pool, p, n) /* p = n elements from the pool, or the caller returns WEPP_ENOMEM */ \
+    do { if (hipError_t _e = (pool).get(&(p), (n))) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
+
+template <int N> struct DevEvents {                     // the N events of a call; destroys those that were created
+    hipEvent_t ev[N] = {};
+    int n = 0;                         // created so far
+    ~DevEvents() { while (n > 0) (void)hipEventDestroy(ev[--n]); }
+    int create() {
+        for (; n < N; n++) { hipEvent_t& x = ev[n]; HIP_TRY(hipEventCreate(&x)); }
+        return WEPP_OK;
+    }
+    hipEvent_t operator[](int i) const { return ev[i]; }
+};
+
+// the reference's preconditions on a read batch, made explicit (read_off / start / end / degree are non-null when n_reads > 0,
+// read_word when there are words): WEPP_OK, or WEPP_EINVAL with the message set.  *total_degree receives the sum of the degrees.
 int epp_validate_reads(const wepp_epp_reads* rd, long long* total_degree);
 // order[s] = the read at place s of the (start, end, index) order: two stable counting passes when the
 // window bounds are genome positions, a comparison sort otherwise
 void epp_window_order(const wepp_epp_reads* rd, std::vector<uint32_t>& order);
 
-// The argument checks of the entry points that take a selection (assign_capi.cpp), in the order they are made:
-// what can be said about the selection without the handle; the handle, the range of the indices and the read
-// arrays; then (after the entry point has looked at its own outputs) genome_size, the read words and the reads'
-// preconditions.  WEPP_OK, or the code with the message set.  `out` is only compared with null.
+struct DevReads {                      // a read batch on the device
+    uint32_t R = 0; uint64_t W = 0;    // reads, words of all reads
+    uint32_t *read_off = nullptr, *read_word = nullptr, *order = nullptr;
+    int32_t *start = nullptr, *end = nullptr, *degree = nullptr;
+};
+int alloc_reads(DevPool& pool, uint32_t R, uint64_t W, DevReads* reads);   // the six blocks of R reads with W words: WEPP_OK or WEPP_ENOMEM
+int upload_reads(DevPool& pool, const wepp_epp_reads* rd, const std::vector<uint32_t>& order, hipStream_t stream, DevReads* reads);   // ... filled with rd (n_reads > 0) in `order`
+
+// The argument checks of the entry points that take a selection, in the order they are made: what can be said about the
+// selection without the handle; the handle, the range of the indices and the read arrays; then (after the entry point has looked at its
+// own outputs) genome_size, the read words and the reads' preconditions.  WEPP_OK, or the code with the message set.  `out` is only compared with null.
 int assign_check_selection(const wepp_epp_reads* rd, const void* out, uint32_t n_sel, const uint32_t* sel);
 int assign_check_handle(const wepp_mat_t* mat, const wepp_epp_reads* rd, uint32_t n_sel, const uint32_t* sel);
 int assign_check_reads(const wepp_epp_reads* rd, uint32_t genome_size);
+// their two scans, shared with the pivots of neighbors_capi.cpp: "<name>[k] = .. is not an arena index ..", "haplotype .. is <twice>"
+int check_arena_indices(const char* name, uint32_t n, const uint32_t* idx, uint32_t N);
+int check_distinct(uint32_t n, const uint32_t* idx, const char* twice);
 
 // the selection's genotype table on the device (launch_assign_tables), its blocks taken from `pool`
 struct AssignTable {
@@ -80,5 +105,13 @@ struct AssignTable {
 // the device work.  WEPP_OK, WEPP_ELIMIT (table size, 16-bit prefix counts), WEPP_ENOMEM or WEPP_EDEVICE.
 int assign_build_table(wepp_mat_t* mat, DevPool& pool, uint32_t n_sel, const uint32_t* sel, hipStream_t stream,
                        hipEvent_t begin, hipEvent_t end, AssignTable* table);
+
+// k_assign's arguments for `reads` against the table of K haplotypes: genome_size, cover_words and the outputs stay the caller's
+inline AssignArgs assign_args(const AssignTable& tab, uint32_t K, const DevReads& reads) {
+    AssignArgs a{};
+    a.R = reads.R; a.K = K; a.Kp = tab.Kp; a.max_pos = tab.max_pos; a.geno = tab.geno; a.pre = tab.pre;
+    a.read_off = reads.read_off; a.read_word = reads.read_word; a.start = reads.start; a.end = reads.end; a.degree = reads.degree; a.order = reads.order;
+    return a;
+}
 
 }  // namespace wepp

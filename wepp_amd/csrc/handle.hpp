@@ -1,5 +1,6 @@
-// handle.hpp -- the object behind wepp_mat_t and the small helpers the C-ABI translation
-// units (capi.cpp, epp_capi.cpp) share.
+// handle.hpp -- the object behind wepp_mat_t and the small helpers the C-ABI translation units (capi.cpp and
+// the *_capi.cpp of the WEPP entry points) share.  It compiles against the emulated runtime of tests/cxx/hip_emu too:
+// tests/epp_emu.py runs the entry points' own host code on a handle made there.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,6 +20,10 @@
 #include "tunables.hpp"
 
 using namespace wepp;
+
+// a device block of the handle's cache: its size and the most bytes a call ever asked of it (the rest is rounding).
+// `asked` is not used by the product: the emulation's guard check (tests/cxx/epp_emu.cpp) looks for stores past it.
+struct DevBlock { void* ptr; size_t bytes, asked; };
 
 // What ONE placement call in flight needs of its own: workspace, routing counters, the side streams its launch
 // chains run on.  A handle has two: the sub-batches of wepp_place_batch alternate between them, so that the routing
@@ -77,8 +82,8 @@ struct wepp_mat {
     // tens of milliseconds); a call takes the blocks that fit and hands everything back when it returns.  Freed
     // with the handle (release() has selected the device by then).
     struct DevBlockCache {
-        std::vector<std::pair<void*, size_t>> blocks;
-        ~DevBlockCache() { for (auto& b : blocks) (void)hipFree(b.first); }
+        std::vector<DevBlock> blocks;
+        ~DevBlockCache() { for (auto& b : blocks) (void)hipFree(b.ptr); }
     } epp_cache;
     // wepp_epp_neighbors (neighbors_capi.cpp): one past the last pre-order index of every subtree, derived from
     // parent_dfs and uploaded by the first call (in `allocs`); columns per pass forced by WEPP_NBR_PASS_COLS

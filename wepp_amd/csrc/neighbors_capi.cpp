@@ -11,9 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "assign.hpp"
 #include "epp_host.hpp"
-#include "handle.hpp"
 #include "neighbors.hpp"
 #include "staged_copy.hpp"
 
@@ -27,17 +25,8 @@ int check_pivots(const wepp_mat_t* mat, uint32_t n_piv, const uint32_t* piv, int
     if (n_piv == 0) return set_error(WEPP_EINVAL, "no pivots: n_piv must be at least 1");
     if (form != WEPP_NBR_TO_PIVOT && form != WEPP_NBR_FROM_PIVOT)
         return set_error(WEPP_EINVAL, "unknown form " + std::to_string(form) + ": WEPP_NBR_TO_PIVOT or WEPP_NBR_FROM_PIVOT");
-    const uint32_t N = mat->dev.N;
-    for (uint32_t k = 0; k < n_piv; k++)
-        if (piv[k] >= N)
-            return set_error(WEPP_EINVAL, "piv[" + std::to_string(k) + "] = " + std::to_string(piv[k]) + " is not an arena index of this tree (" +
-                                              std::to_string(N) + " haplotypes)");
-    std::vector<uint32_t> sorted(piv, piv + n_piv);
-    std::sort(sorted.begin(), sorted.end());
-    for (uint32_t k = 1; k < n_piv; k++)
-        if (sorted[k] == sorted[k - 1])
-            return set_error(WEPP_EINVAL, "haplotype " + std::to_string(sorted[k]) + " is a pivot more than once");
-    return WEPP_OK;
+    if (int rc = check_arena_indices("piv", n_piv, piv, mat->dev.N)) return rc;
+    return check_distinct(n_piv, piv, "a pivot more than once");
 }
 
 // the handle's dfs_end (device) and its forced pass size, made by the first call
@@ -76,31 +65,28 @@ int run(wepp_mat_t* mat, uint32_t K, const uint32_t* piv, uint32_t radius, int f
     const uint32_t nblk = nbr_scan_blocks((uint32_t)rows);
 
     hipStream_t stream = nullptr;
-    DevPool pool(mat);
-    hipError_t e;
-#define GET(pl, p, n) if ((e = pl.get(&p, (n))) != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    DevPool pool(mat->epp_cache);
     int32_t *d_field, *d_over = nullptr, *d_tover = nullptr;
     uint32_t *d_piv, *d_bsum, *d_bcnt = nullptr, *d_top = nullptr, *d_tend = nullptr, *d_nreg = nullptr, *d_nlist = nullptr;
     uint8_t* d_skip = nullptr;
     unsigned long long* d_off = nullptr;
     char* d_temp = nullptr;
     size_t temp_bytes = 0;
-    GET(pool, d_piv, K) GET(pool, d_field, rows * Es_max) GET(pool, d_bsum, (size_t)nblk * Es_max)
+    DEV_GET(pool, d_piv, K); DEV_GET(pool, d_field, rows * Es_max); DEV_GET(pool, d_bsum, (size_t)nblk * Es_max);
     if (out) {
-        GET(pool, d_over, rows * Es_max) GET(pool, d_bcnt, (size_t)nblk * Es_max) GET(pool, d_top, Es_max) GET(pool, d_tend, Es_max)
-        GET(pool, d_tover, Es_max) GET(pool, d_nreg, Es_max) GET(pool, d_nlist, (size_t)Es_max + 1) GET(pool, d_off, (size_t)Es_max + 1)
+        DEV_GET(pool, d_over, rows * Es_max); DEV_GET(pool, d_bcnt, (size_t)nblk * Es_max); DEV_GET(pool, d_top, Es_max); DEV_GET(pool, d_tend, Es_max);
+        DEV_GET(pool, d_tover, Es_max); DEV_GET(pool, d_nreg, Es_max); DEV_GET(pool, d_nlist, (size_t)Es_max + 1); DEV_GET(pool, d_off, (size_t)Es_max + 1);
         HIP_TRY(assign_scan_temp_bytes(Es_max, &temp_bytes));
-        GET(pool, d_temp, temp_bytes)
+        DEV_GET(pool, d_temp, temp_bytes);
         if (skip) {
-            GET(pool, d_skip, N)
+            DEV_GET(pool, d_skip, N);
             HIP_TRY(hipMemcpyAsync(d_skip, skip, N, hipMemcpyHostToDevice, stream));
         }
     }
     HIP_TRY(hipMemcpyAsync(d_piv, piv, (size_t)K * 4, hipMemcpyHostToDevice, stream));
 
-    hipEvent_t ev[5];
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 5; i++) (void)hipEventDestroy(e[i]); } } evg{ev};
+    DevEvents<5> ev;
+    if (int rc = ev.create()) return rc;
 
     NbrTree t{};
     t.N = N; t.max_pos = mat->dev.max_pos;
@@ -113,7 +99,7 @@ int run(wepp_mat_t* mat, uint32_t K, const uint32_t* piv, uint32_t radius, int f
     bool short_lists = false;
     for (uint32_t k0 = 0; k0 < K; k0 += pass_cols) {
         const uint32_t Kc = std::min(pass_cols, K - k0), Es = nbr_stride(Kc);
-        DevPool pass_pool(mat);         // the pass's genotype table and lists: back in the cache for the next pass
+        DevPool pass_pool(mat->epp_cache);        // the pass's genotype table and lists: back in the cache for the next pass
         AssignTable tab;
         if (int rc = assign_build_table(mat, pass_pool, Kc, piv + k0, stream, ev[0], ev[1], &tab)) return rc;
 
@@ -152,7 +138,7 @@ int run(wepp_mat_t* mat, uint32_t K, const uint32_t* piv, uint32_t radius, int f
             uint32_t* d_node = nullptr;
             int32_t* d_dist = nullptr;
             if (need && !short_lists) {
-                GET(pass_pool, d_node, need) GET(pass_pool, d_dist, need)
+                DEV_GET(pass_pool, d_node, need); DEV_GET(pass_pool, d_dist, need);
                 HIP_TRY(launch_nbr_write(N, Kc, d_field, d_over, Es, d_top, d_tend, d_tover, d_skip, d_bcnt, d_off, d_node, d_dist, stream));
             }
             HIP_TRY(hipEventRecord(ev[3], stream));
@@ -167,7 +153,6 @@ int run(wepp_mat_t* mat, uint32_t K, const uint32_t* piv, uint32_t radius, int f
         if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) g_last.tables_ms += ms;
         if (hipEventElapsedTime(&ms, ev[1], ev[2]) == hipSuccess) g_last.field_ms += ms;
     }
-#undef GET
     if (out) {
         out->nbr_off[K] = base;
         if (short_lists)

@@ -8,13 +8,10 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstring>
 #include <string>
 #include <vector>
 
-#include "assign.hpp"
 #include "epp_host.hpp"
-#include "handle.hpp"
 #include "resolve.hpp"
 #include "resolve_host.hpp"
 #include "staged_copy.hpp"
@@ -64,7 +61,6 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
         zero_outputs(out, M, K);
         return WEPP_OK;
     }
-    const uint64_t W = rd->read_off[R];
     const uint32_t KW = (K + 31) / 32;
     const bool want_lists = out->rel_off != nullptr;
 
@@ -74,35 +70,27 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
 
     HIP_TRY(hipSetDevice(mat->device));
     hipStream_t stream = nullptr;
-    DevPool pool(mat);
-    hipError_t e;
-#define GET(p, n) if ((e = pool.get(&p, (n))) != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    uint32_t *d_off, *d_word, *d_order, *d_rpos, *d_rword, *d_ridx, *d_counts, *d_ncov, *d_nmask;
-    int32_t *d_start, *d_end, *d_degree;
+    DevPool pool(mat->epp_cache);
+    DevReads reads, touched;
+    if (int rc = upload_reads(pool, rd, order, stream, &reads)) return rc;
+    uint32_t *d_rpos, *d_rword, *d_ridx, *d_counts, *d_ncov, *d_nmask;
     unsigned long long* d_scans;
     const size_t R1 = (size_t)R + 1;
-    GET(d_off, R1) GET(d_word, W) GET(d_order, R) GET(d_start, R) GET(d_end, R) GET(d_degree, R)
-    GET(d_rpos, M) GET(d_rword, M) GET(d_ridx, M) GET(d_counts, 4 * R1) GET(d_scans, 4 * R1) GET(d_ncov, M) GET(d_nmask, M)
-    HIP_TRY(hipMemcpyAsync(d_off, rd->read_off, R1 * 4, hipMemcpyHostToDevice, stream));
-    if (W) HIP_TRY(hipMemcpyAsync(d_word, rd->read_word, W * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_start, rd->start, (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_end, rd->end, (size_t)R * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(d_degree, rd->degree, (size_t)R * 4, hipMemcpyHostToDevice, stream));
+    DEV_GET(pool, d_rpos, M); DEV_GET(pool, d_rword, M); DEV_GET(pool, d_ridx, M); DEV_GET(pool, d_counts, 4 * R1);
+    DEV_GET(pool, d_scans, 4 * R1); DEV_GET(pool, d_ncov, M); DEV_GET(pool, d_nmask, M);
     HIP_TRY(hipMemcpyAsync(d_rpos, res_pos.data(), (size_t)M * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_rword, res_sorted.data(), (size_t)M * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(d_ridx, res_idx.data(), (size_t)M * 4, hipMemcpyHostToDevice, stream));
 
-    hipEvent_t ev[6];
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int i = 0; i < 6; i++) (void)hipEventDestroy(e[i]); } } evg{ev};
+    DevEvents<6> ev;
+    if (int rc = ev.create()) return rc;
     HIP_TRY(hipEventRecord(ev[0], stream));
 
     // ---- mark: count, scans ------------------------------------------------------------------------------
     MarkArgs ma{};
     ma.R = R; ma.M = M;
     ma.res_pos = d_rpos; ma.res_word = d_rword; ma.res_idx = d_ridx;
-    ma.read_off = d_off; ma.read_word = d_word; ma.start = d_start; ma.end = d_end; ma.degree = d_degree; ma.order = d_order;
+    ma.read_off = reads.read_off; ma.read_word = reads.read_word; ma.start = reads.start; ma.end = reads.end; ma.degree = reads.degree; ma.order = reads.order;
     ma.n_rel = d_counts; ma.n_words = d_counts + R1; ma.touched = d_counts + 2 * R1; ma.touched_place = d_counts + 3 * R1;
     ma.rel_at = d_scans; ma.word_at = d_scans + R1; ma.compact = d_scans + 2 * R1; ma.place_at = d_scans + 3 * R1;
     HIP_TRY(hipMemsetAsync(d_counts, 0, 4 * R1 * 4, stream));       // (the R-th element of each: the scans' totals)
@@ -113,7 +101,7 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
         size_t temp_bytes = 0;
         HIP_TRY(assign_scan_temp_bytes(R, &temp_bytes));
         char* d_temp;
-        GET(d_temp, temp_bytes)
+        DEV_GET(pool, d_temp, temp_bytes);
         for (int i = 0; i < 4; i++)
             HIP_TRY(launch_assign_scan(d_counts + i * R1, d_scans + i * R1, R, d_temp, temp_bytes, stream));
     }
@@ -130,13 +118,13 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
     if (W2 >= (1ull << 32)) return set_error(WEPP_ELIMIT, "more than 2^32 read words in the touched reads after the insertions");
 
     // ---- mark: the touched reads as a batch, the relations mutation-major ---------------------------------------
-    uint32_t *d_toff, *d_tword, *d_torder, *d_key, *d_val, *d_key2, *d_val2;
-    int32_t *d_tstart, *d_tend, *d_tdegree;
+    uint32_t *d_key, *d_val, *d_key2, *d_val2;
     unsigned long long* d_reloff;
-    GET(d_toff, (size_t)T + 1) GET(d_tword, W2) GET(d_torder, T) GET(d_tstart, T) GET(d_tend, T) GET(d_tdegree, T)
-    GET(d_key, n_rel) GET(d_val, n_rel) GET(d_key2, n_rel) GET(d_val2, n_rel) GET(d_reloff, (size_t)M + 1)
-    ma.out_off = d_toff; ma.out_word = d_tword; ma.out_start = d_tstart; ma.out_end = d_tend; ma.out_degree = d_tdegree;
-    ma.out_order = d_torder; ma.rel_key = d_key; ma.rel_val = d_val; ma.n_covered = d_ncov; ma.n_masked = d_nmask;
+    if (int rc = alloc_reads(pool, T, W2, &touched)) return rc;
+    DEV_GET(pool, d_key, n_rel); DEV_GET(pool, d_val, n_rel); DEV_GET(pool, d_key2, n_rel); DEV_GET(pool, d_val2, n_rel);
+    DEV_GET(pool, d_reloff, (size_t)M + 1);
+    ma.out_off = touched.read_off; ma.out_word = touched.read_word; ma.out_start = touched.start; ma.out_end = touched.end;
+    ma.out_degree = touched.degree; ma.out_order = touched.order; ma.rel_key = d_key; ma.rel_val = d_val; ma.n_covered = d_ncov; ma.n_masked = d_nmask;
     HIP_TRY(launch_resolve_write(ma, stream));
     {
         uint32_t key_bits = 1;
@@ -144,7 +132,7 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
         size_t temp_bytes = 0;
         HIP_TRY(resolve_sort_temp_bytes(n_rel, key_bits, &temp_bytes));
         char* d_temp;
-        GET(d_temp, temp_bytes)
+        DEV_GET(pool, d_temp, temp_bytes);
         HIP_TRY(launch_resolve_sort(d_key, d_key2, d_val, d_val2, n_rel, key_bits, d_temp, temp_bytes, stream));
     }
     HIP_TRY(launch_resolve_offsets(d_key2, n_rel, M, d_reloff, stream));
@@ -162,16 +150,15 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
     int32_t* d_min;
     unsigned long long *d_sdeg, *d_ties, *d_hdeg;
     long long* d_bdeg;
-    GET(d_min, T) GET(d_nepp, (size_t)T + 1) GET(d_sreads, Kp) GET(d_sdeg, Kp) GET(d_cover, 1) GET(d_ties, (size_t)T * nslabs * 4)
-    GET(d_hreads, (size_t)M * K) GET(d_hdeg, (size_t)M * K) GET(d_bdeg, M) GET(d_bmask, (size_t)M * KW)
+    DEV_GET(pool, d_min, T); DEV_GET(pool, d_nepp, (size_t)T + 1); DEV_GET(pool, d_sreads, Kp); DEV_GET(pool, d_sdeg, Kp); DEV_GET(pool, d_cover, 0);
+    DEV_GET(pool, d_ties, (size_t)T * nslabs * 4); DEV_GET(pool, d_hreads, (size_t)M * K); DEV_GET(pool, d_hdeg, (size_t)M * K);
+    DEV_GET(pool, d_bdeg, M); DEV_GET(pool, d_bmask, (size_t)M * KW);
     HIP_TRY(hipMemsetAsync(d_sreads, 0, (size_t)Kp * 4, stream));
     HIP_TRY(hipMemsetAsync(d_sdeg, 0, (size_t)Kp * 8, stream));
-    AssignArgs a{};
-    // genome_size 0: no site is inside the genome, so k_assign sets no coverage bit and never looks at `cover`;
+    // genome_size 0: no site is inside the genome, so k_assign sets no coverage bit and never looks at `cover` (0 elements);
     // min_dist, n_epp, sel_reads and sel_degree are scratch here, the tie masks are what is wanted
-    a.R = T; a.K = K; a.Kp = Kp; a.max_pos = tab.max_pos; a.genome_size = 0; a.cover_words = 0;
-    a.geno = tab.geno; a.pre = tab.pre;
-    a.read_off = d_toff; a.read_word = d_tword; a.start = d_tstart; a.end = d_tend; a.degree = d_tdegree; a.order = d_torder;
+    AssignArgs a = assign_args(tab, K, touched);
+    a.genome_size = 0; a.cover_words = 0;
     a.min_dist = d_min; a.n_epp = d_nepp; a.ties = d_ties;
     a.sel_reads = d_sreads; a.sel_degree = d_sdeg; a.cover = d_cover;
     HIP_TRY(launch_assign(a, stream));
@@ -184,7 +171,7 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
     HIP_TRY(hipMemsetAsync(d_hdeg, 0, (size_t)M * K * 8, stream));
     TallyArgs ta{};
     ta.M = M; ta.K = K; ta.Kp = Kp;
-    ta.rel_off = d_reloff; ta.rel_read = d_val2; ta.compact = ma.compact; ta.degree = d_tdegree; ta.ties = d_ties;
+    ta.rel_off = d_reloff; ta.rel_read = d_val2; ta.compact = ma.compact; ta.degree = touched.degree; ta.ties = d_ties;
     ta.hap_reads = d_hreads; ta.hap_degree = d_hdeg;
     HIP_TRY(launch_resolve_tally(ta, (longest + RES_CHUNK - 1) / RES_CHUNK, stream));
     HIP_TRY(launch_resolve_best(d_hreads, d_hdeg, M, K, d_bdeg, d_bmask, stream));
@@ -201,7 +188,6 @@ extern "C" int wepp_epp_resolve(wepp_mat_t* mat, const wepp_epp_reads* rd, uint3
     // too small a buffer leaves the lists out, everything else stands
     const bool short_lists = want_lists && (n_rel > out->rel_capacity || !out->rel_read);
     if (want_lists && !short_lists) HIP_TRY(d2h_staged(out->rel_read, d_val2, n_rel * 4, stream));
-#undef GET
     (void)hipEventElapsedTime(&g_last.mark_ms, ev[0], ev[1]);
     (void)hipEventElapsedTime(&g_last.tables_ms, ev[2], ev[3]);
     (void)hipEventElapsedTime(&g_last.assign_ms, ev[3], ev[4]);
