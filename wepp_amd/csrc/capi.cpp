@@ -41,6 +41,7 @@ void release(wepp_mat* h) {
         }
         if (L.fork_ev) (void)hipEventDestroy(L.fork_ev);
         if (L.route_ev) (void)hipEventDestroy(L.route_ev);
+        if (L.info_ev) (void)hipEventDestroy(L.info_ev);
         if (L.d_seed_heavy) (void)hipFree(L.d_seed_heavy);
     }
     if (h->io_in) (void)hipFree(h->io_in);
@@ -371,6 +372,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
         }
         if (e == hipSuccess) e = hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&L.route_ev, hipEventDisableTiming);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&L.info_ev, hipEventDisableTiming);
     }
     for (uint32_t i = 0; i < wepp_mat::kRing && e == hipSuccess; i++) {
         e = hipEventCreate(&h->ev0[i]);
@@ -485,7 +487,7 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
 // handle:
 //   - the tree and everything built from it (read-only here);
 //   - the event ring (a slot claimed atomically);
-//   - the hints job_events, ww_by_jobs and expect_jobs8 (atomics; they choose how the next call cuts its work, never its results);
+//   - the hints job_events, ww_by_jobs, expect_jobs8 and expect_lists (atomics; they choose how the next call cuts its work, never its results);
 //   - the call statistics (stat_mu) and the device counters d_work (device atomics, summed over both lanes);
 //   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
 int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
@@ -594,9 +596,9 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     constexpr uint32_t PLAN_STREAM = MAX_STREAMS - 7;
     // Streams of a call.  The caller's stream runs k_route and, right behind it (no cross-stream wait: ~25 us), the
     // chunked walks of the first class -- the longest chain of the common case; the plain walks and the second chunked
-    // class start from the routing kernel's event on side streams; everything the HOST has to size -- k_scatter, the
-    // counters' copy, the sweeps, the planned walks -- lives on the plan stream `ps`, off the walks' path.  All of them
-    // join the caller's stream at the end.
+    // class start from the routing kernel's event on side streams; everything the HOST has to size -- the counters'
+    // copy, k_scatter, the sweeps, the planned walks -- lives on the plan stream `ps`, off the walks' path.  What ran
+    // there behind the copy joins the caller's stream at the end; a call that launched nothing there joins nothing.
     const bool walking = mat->use_walk && walk_max_events;
     hipStream_t ps = walking ? L.side[PLAN_STREAM] : stream;
     // WEPP_STEP_UNFUSED=1 (A/B aid): the launches behind k_route as they were before k_step -- the plain walks, k_walk_wave
@@ -609,6 +611,23 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // handle's previous call held such reads -- two launches that find nothing, a fork and a join otherwise --, else from
     // the counters like the 16-entry class.  A hint: a call it misleads launches the class late and places every read.
     const bool jobs8_blind = step_unfused || mat->expect_jobs8.load(std::memory_order_relaxed) != 0;
+    // k_scatter (the reads grouped by plan: `list`) is read by the launches the host plans and by nothing else -- sweeps,
+    // window tiles, arena sweeps, seeds, the chunked classes it plans itself, and their sorts.  A sequencing run's batch
+    // holds none: the kernel, a pass over every read, runs only when the counters name a consumer (lists_needed below),
+    // LATE, behind the counters' copy.  A handle whose previous call had consumers launches it BLIND behind the copy, as
+    // every call did before, and loses nothing.  A hint like expect_jobs8: a call it misleads pays the late launch or an
+    // idle kernel, never a result.  Bit 0 of expect_lists = expect consumers; bit 1 = the last blind launch it asked for
+    // found none: the next call WITH consumers then does not set bit 0 again, so that batches of both kinds in turn do
+    // not pay an idle kernel and a join in front of every other one of them.  WEPP_SCATTER_BLIND=1 (A/B aid),
+    // WEPP_STEP_UNFUSED=1 and a call without walks (every read is listed, ps is the caller's stream): always blind.
+    const uint32_t lists_hint = mat->expect_lists.load(std::memory_order_relaxed);
+    const bool scatter_blind = !walking || step_unfused || tun.scatter_blind || (lists_hint & 1u) != 0;
+    bool need_lists = !walking;       // (from the counters, once the host has them)
+    bool scattered = false;           // k_scatter of this call is queued on ps
+    auto scatter = [&]() -> hipError_t {
+        scattered = true;
+        return launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps);
+    };
     // one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
     auto blind_class = [&](uint32_t cls, hipStream_t q, bool fork_q) -> hipError_t {
         hipError_t e = hipSuccess;
@@ -635,7 +654,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // (... and then reads of up to 16 events walk plainly, as before the waves: 100 000 reads with 7 - 16 events are
     // nothing to a walk launch -- its time is its longest walk -- and 0.3 ms as jobs)
     const uint32_t walk_limit = (ww_jobs && !tun.ww_fixed) ? std::max(walk_max_events, WALK_MAX_EVENTS_BY_JOBS) : walk_max_events;
-    auto route = [&]() -> int {
+    auto route = [&](bool first) -> int {
         // the counters alternate between two sets: this call's set is zero (cleared at creation or by the
         // previous k_route), and this k_route clears the other one for the next call
         tier_info = L.d_info + L.info_idx * TI_WORDS;
@@ -688,16 +707,32 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                 HIP_TRY(hipEventRecord(L.join_ev[BLIND16_STREAM], L.side[BLIND16_STREAM]));
             }
             HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
+            // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
+            // below), so their copy goes directly behind the wait, in front of any k_scatter, and an event of its own
+            // tells the host when it has landed -- whatever is queued behind it.  The host then returns, and enqueues
+            // the next call's k_route, while k_step still runs.  (A second routing pass after the workspace moved
+            // copies nothing: the counters are the same, and the host has filled TI_OFF into h_info.)
+            if (first) {
+                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+                HIP_TRY(hipEventRecord(L.info_ev, ps));
+            }
+            scattered = false;
+            if (scatter_blind || need_lists) HIP_TRY(scatter());
+        } else {
+            // (no walks: every read is listed, on the caller's stream, the counters behind the lists as ever)
+            HIP_TRY(scatter());
+            if (first) {
+                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+                HIP_TRY(hipEventRecord(L.info_ev, ps));
+            }
         }
-        HIP_TRY(launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps));
         return WEPP_OK;
     };
 
     {
-        int rc = route();
+        int rc = route(true);
         if (rc != WEPP_OK) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
     // the host sizes the launches from the counters, and the GPU idles until it has: poll for them (a
     // blocking wait adds its wake-up, ~15 us per call, to that idle time) ...
     {
@@ -707,20 +742,61 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         hipError_t q = hipErrorNotReady;
         const auto t_poll = std::chrono::steady_clock::now();
         for (;;) {
-            q = hipStreamQuery(ps);
+            q = hipEventQuery(L.info_ev);
             if (q != hipErrorNotReady) break;
             const auto waited = std::chrono::steady_clock::now() - t_poll;
             if (waited > std::chrono::milliseconds(2)) break;
             if (waited > std::chrono::microseconds(200)) std::this_thread::yield();
         }
         (void)hipGetLastError();   // "not ready" is not an error: keep it out of the launchers' hipGetLastError()
-        if (q != hipSuccess) HIP_TRY(hipStreamSynchronize(ps));
+        if (q != hipSuccess) HIP_TRY(hipEventSynchronize(L.info_ev));
+    }
+    if (walking) {
+        // TI_OFF = the exclusive prefix sum of TI_COUNT, and the total behind the last plan: what k_scatter writes on
+        // the device, formed here because the copy no longer waits for it (the copy has landed: h_info is the host's)
+        uint32_t off = 0;
+        for (uint32_t t = 0; t < MAX_PLANS; t++) { L.h_info[TI_OFF + t] = off; off += L.h_info[TI_COUNT + t]; }
+        L.h_info[TI_OFF + MAX_PLANS] = off;
     }
     const uint32_t* info = L.h_info;
     if (tun.debug_plans)
         fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
                 n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
                 info[TI_CCUR + 1], info[TI_JCUR], info[TI_JCUR + 1], info[TI_JOVER], info[TI_JOVER + 1]);
+    const bool blind_walks = walking;       // (launched behind k_route, joined below)
+    // Who reads `list`: decided HERE, from the counters, for the whole call.  A plan with reads is a consumer unless its
+    // class is placed out of k_route's own tables: the plain walk classes always, a chunked class that fitted its blind
+    // tables (TI_JOVER == 0: launched blind or from the counters below, never by a plan of the host).
+    auto lists_needed = [&]() {
+        for (uint32_t id = 0; id < MAX_PLANS; id++) {
+            if (!info[TI_COUNT + id]) continue;
+            const uint32_t cls = plan_class(id);
+            if (cls == PLAN_WALK8 || cls == PLAN_WALK16) continue;
+            if ((cls == PLAN_WALKC8 || cls == PLAN_WALKC16) && !info[TI_JOVER + (cls - PLAN_WALKC8)]) continue;
+            return true;
+        }
+        return false;
+    };
+    const char* scatter_mode = "blind";
+    if (walking) {
+        need_lists = lists_needed();
+        // (the hint of the next call: see lists_hint above)
+        mat->expect_lists.store(need_lists ? ((lists_hint & 2u) ? 0u : 1u) : ((lists_hint & 1u) ? 2u : (lists_hint & 2u)), std::memory_order_relaxed);
+        if (!scattered) {
+            scatter_mode = need_lists ? "late" : "none";
+            // LATE: the hint said no and the counters say yes.  On ps, behind the copy and in front of everything that
+            // reads the lists (all of it is launched below, on ps or on streams forked from it).
+            if (need_lists) HIP_TRY(scatter());
+        }
+    }
+    // Hazards of a call WITHOUT k_scatter (scattered == false from here on): nothing of this call reads blk_counts,
+    // tier_of's slots or slot_in_blk -- per lane, rewritten by the lane's next k_route -- and nothing runs on ps behind
+    // the copy the host has seen complete, so ps needs no join.  k_step reads TI_WCUR / TI_WWCUR of this call's counter
+    // set on the caller's stream, in front of the next k_route, which clears the OTHER set; the set after that clears
+    // this one, behind everything this call put on the caller's stream.  A k_scatter that was launched, blind or late,
+    // reads those per-lane buffers and writes TI_OFF into this call's set: it and every consumer behind it are joined
+    // into the caller's stream below, before the call returns.
+    if (tun.debug_plans) fprintf(stderr, "[lists] scatter=%s plan stream joined=%d\n", scatter_mode, (int)(walking && scattered));
     for (uint32_t cc = 0; cc < 2; cc++) {
         const uint64_t ev = (uint64_t)info[TI_EVENTS + cc] << 6;
         const uint32_t je = (uint32_t)std::min<uint64_t>(WALK_JOB_EVENTS_MAX, std::max<uint64_t>(WALK_JOB_EVENTS, ev / WALK_TARGET_JOBS));
@@ -732,7 +808,6 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         const uint64_t scale = std::max<uint64_t>(1, ((uint64_t)n_reads + (1u << 20) - 1) >> 20);
         mat->ww_by_jobs.store((info[TI_WWCAND] > WW_CALL_MAX_SMALL * scale || info[TI_WWCAND + 1] > WW_CALL_MAX_BIG * scale) ? 1u : 0u, std::memory_order_relaxed);
     }
-    const bool blind_walks = mat->use_walk && walk_max_events;       // (launched behind k_route, joined below)
     bool late16[2] = {false, false}, late8 = false;
     if (blind_walks) {
         // the 8-entry job class when the hint did not expect it, and the hint of the next call
@@ -881,10 +956,11 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (ws_moved) {
             // the workspace moved: redo the (cheap) routing into the new buffer
             carve();
-            rc = route();
+            rc = route(false);
             if (rc != WEPP_OK) return rc;
         }
     }
+    if (!scattered && (np || arena_n || seed_n || walkc[0].n || walkc[1].n)) return set_error(WEPP_EDEVICE, "a planned launch without its read list");
     char* part_base = (char*)L.ws + fixed_bytes;
     // (the workspace may have moved above: every pointer into it is taken from here on)
     for (uint32_t cc = 0; cc < 2; cc++)
@@ -1142,9 +1218,12 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     }
     for (uint32_t i = 0; i < n_joins; i++) HIP_TRY(hipStreamWaitEvent(ps, L.join_ev[joins[i]], 0));
     if (blind_walks) {
-        // the plan stream and the blind walks' side streams join the caller's stream
-        HIP_TRY(hipEventRecord(L.join_ev[PLAN_STREAM], ps));
-        HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[PLAN_STREAM], 0));
+        // the plan stream, when something ran on it behind the counters' copy (k_scatter and what reads its lists: no
+        // consumer is launched without it), and the blind walks' side streams join the caller's stream
+        if (scattered) {
+            HIP_TRY(hipEventRecord(L.join_ev[PLAN_STREAM], ps));
+            HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[PLAN_STREAM], 0));
+        }
         if (step_unfused) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 1], 0));
         if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 2], 0));
         if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[BLIND16_STREAM], 0));

@@ -409,7 +409,10 @@ hipError_t launch_excess(const DevMAT& m, const uint32_t* d_read_off, const uint
 hipError_t sweep_set_max_lds(uint32_t bytes);
 
 // layout of tier_info (uint32), indexed by plan id: counts, max entries of one read, offsets into the list
-// then, per chunked class and stream, the jobs of its chunked walks
+// then, per chunked class and stream, the jobs of its chunked walks.  Everything but TI_OFF is final when k_route ends;
+// TI_OFF (MAX_PLANS + 1 words: the exclusive prefix sum of TI_COUNT and the total) is written by k_scatter, which a
+// placement call launches only when a launch reads the list -- its host forms the same words in the pinned copy from
+// the counts (capi.cpp: place_device), so the copy of the block does not wait for k_scatter.
 constexpr uint32_t TI_COUNT = 0, TI_MAXK = MAX_PLANS, TI_OFF = 2 * MAX_PLANS, TI_JOBS = 3 * MAX_PLANS + 1,
                    TI_OPEN = TI_JOBS + 2 * MAX_STREAMS,      // [4] deepest stack of the walk classes (WALK8, WALK16, WALKC8, WALKC16)
                    TI_EVENTS = TI_OPEN + 4,                  // [2] events (in units of 64) of the reads of the two chunked classes

@@ -42,6 +42,7 @@ struct PlaceLane {
     hipStream_t side[MAX_STREAMS] = {};
     hipEvent_t fork_ev = nullptr, join_ev[MAX_STREAMS] = {};
     hipEvent_t route_ev = nullptr;    // behind k_route: the plain walks start from here on their side stream, before the host has the counters
+    hipEvent_t info_ev = nullptr;     // behind the copy of tier_info to h_info: the host polls it, whatever is queued behind the copy
     // k_seed's table of samples handed to its second pass (seed_kernels.hip), zero between calls.  One per lane: a
     // record names a read of ITS sub-batch, and the finalize kernel writes into its lane's result arrays and clears the
     // count -- the seed chains of two lanes may run at the same time.
@@ -119,6 +120,7 @@ struct wepp_mat {
     hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};
     std::atomic<uint32_t> ww_by_jobs{0};  // the previous call held too many reads with 17 - 256 events for a wave each: this call cuts their walks into jobs (a hint, like job_events)
     std::atomic<uint32_t> expect_jobs8{0};  // the previous call held reads of the 8-entry job class: this call launches the class blind behind k_route, else from the counters (a hint too)
+    std::atomic<uint32_t> expect_lists{0};  // the previous call held reads whose launches read the grouped read list: this call launches k_scatter blind behind the counters' copy, else only once the counters ask for it; bit 1: its last blind launch found no consumer (a hint too: capi.cpp)
     std::atomic<uint64_t> n_timed{0}; // placement calls since the last timing reset (a call claims its slot of the event ring when it starts)
     std::mutex stat_mu;               // the counters below: the sub-batches of a pipelined wepp_place_batch finish on two host threads
     uint64_t plan_reads_in = 0;       // reads of the sub-batches of the current call that have been planned
