@@ -619,6 +619,56 @@ int wepp_epp_distances(wepp_mat_t *mat, uint32_t n_piv, const uint32_t *piv, int
  * (radius test, second scan, tops, counts, lists) */
 int wepp_epp_neighbors_last_timing(double *tables_ms, double *field_ms, double *region_ms);
 
+/* ---- the peak-removal loop -------------------------------------------------- *
+ * Replaces `while (!step(...))` of wepp_filter::filter (src/WEPP/initial_filter.cpp:467-469): step, singular_step,
+ * find_correspondents, remove_read and clear_neighbors (:241-453).  The call runs wepp_epp_map itself (the
+ * fixed-point sums behind hap_score, P = max_parsimony, M = multiplicity and the share q[r] every EPP haplotype of
+ * read r received stay on the device) and delivers the map's outputs too when map_out is given (lists for reads with
+ * multiplicity <= WEPP_MAX_CACHED_EPP_SIZE; a short epp_nodes ends the call with WEPP_ELIMIT before the loop).
+ * With d(r, h) the distance of wepp_epp_assign, a haplotype LIVE when it is not mapped and its score is
+ * > score_epsilon, and full_score = score * sqrt(dist_divergence) (haplotype.hpp:183-185), one step is:
+ *   1. m = the largest full_score over the live haplotypes; the loop ends when there is none or m < score_epsilon.
+ *      The tie group = the live haplotypes with m - full_score < score_epsilon, ordered by tie_rank ascending (the
+ *      place score_comparator, arena.hpp:16-31, gives them through leaf_count and id), lower arena index first among
+ *      equal ranks and when tie_rank is NULL.  (The device gathers the group unordered; the ordering and the walk
+ *      of step 2 run on the host, so the whole group crosses to the host and back once per step.)
+ *   2. the group is walked in that order while fewer than top_n are accepted and accepted + peaks < max_peaks; a
+ *      candidate c is accepted iff old->mutation_distance(c) > peak_radius for every accepted old (the distance of
+ *      WEPP_NBR_FROM_PIVOT with pivot old).  The accepted become mapped and join the peaks in this order.
+ *   3. every haplotype of the WEPP_NBR_FROM_PIVOT region of radius peak_radius of every accepted peak becomes mapped.
+ *   4. every remaining read r with d(r, a) == P[r] for an accepted a leaves the remaining set; it belongs to the FIRST
+ *      such a in the order of step 2, and every haplotype h with d(r, h) == P[r] loses exactly q[r].
+ *   5. the loop ends when peaks >= max_peaks or no read remains.
+ * Outputs: peaks / peak_step / peak_reads / peak_degree / peak_score in selection order (peak_score = the full_score
+ * when chosen, peak_reads / peak_degree = the reads removed for the peak and the sum of their degrees); n_steps = the
+ * steps that accepted a peak; removed_step[r] / removed_peak[r] = the step and the place in `peaks` of the peak that
+ * took read r, -1 / 0xFFFFFFFF for a read that remains; mapped[n]; score_left[n] = the score when the loop ended
+ * (fixed point like hap_score: exactly 0 for a haplotype whose reads are all gone; the scores of mapped haplotypes,
+ * which the reference leaves dependent on its cache, are those of this closed form).
+ * Near ties: the sums are integers, so haplotypes with the same EPP reads tie exactly.  The result is the reference's
+ * whenever, at every step, each live full_score is either within a hair of m or clearly (by more than the fixed-point
+ * error of hap_score) more than score_epsilon below it; in between the reference's own parallel_sort under a
+ * comparator that is no strict weak order decides, and no port can promise its answer.
+ * Conventions: those of wepp_epp_map (codes, messages, limits) and of wepp_epp_assign for the peaks' genotype table.
+ * n_reads == 0: no peaks, WEPP_OK.  top_n == 0 or max_peaks == 0: WEPP_EINVAL.  Serial per handle. */
+typedef struct { uint32_t top_n, max_peaks, peak_radius; double score_epsilon; } wepp_peaks_params;
+   /* defaults 10, 300, 2, 1e-9: TOP_N, MAX_PEAKS, MAX_PEAK_PEAK_MUTATION, SCORE_EPSILON of src/WEPP/config.hpp */
+typedef struct {
+    uint32_t *n_peaks, *n_steps, *n_remaining;      /* [1] each */
+    uint32_t *peaks, *peak_step, *peak_reads;       /* [max_peaks], selection order */
+    int64_t  *peak_degree;  double *peak_score;     /* [max_peaks] */
+    int32_t  *removed_step; uint32_t *removed_peak; /* [n_reads] */
+    uint8_t  *mapped;                               /* [n_nodes] */
+    double   *score_left;                           /* [n_nodes] or NULL */
+} wepp_peaks_out;
+int wepp_epp_peaks(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t genome_size, const wepp_peaks_params *params,
+                   const uint32_t *tie_rank /* [n_nodes] or NULL */, wepp_epp_out *map_out /* or NULL */,
+                   wepp_peaks_out *out);
+/* wall time of the calling thread's last wepp_epp_peaks by phase (ms; every phase ends with the device idle): the map;
+ * leaders, tie groups and the accepted peaks' distance fields; the reads of the accepted peaks; their removal from
+ * the scores (the map's sweep over the subset); the regions that become mapped */
+int wepp_epp_peaks_last_timing(double *map_ms, double *select_ms, double *hits_ms, double *remove_ms, double *clear_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

@@ -15,6 +15,7 @@ SCRATCH=$(mktemp -d)
 trap 'rm -rf "$SCRATCH"' EXIT
 mkdir -p "$SCRATCH/wepp_amd" "$SCRATCH/include"
 cp -r "$ROOT/wepp_amd/csrc" "$SCRATCH/wepp_amd/csrc"
+mkdir -p "$SCRATCH/wepp_amd/host" && cp "$ROOT/wepp_amd/host/peak_select.hpp" "$SCRATCH/wepp_amd/host/"
 cp "$ROOT/include/wepp_place.h" "$SCRATCH/include/"
 rm -f "$SCRATCH"/wepp_amd/csrc/*.o
 EXTRA=()
@@ -25,7 +26,7 @@ done
 SRC=$SCRATCH/wepp_amd/csrc
 FLAGS="-O3 -std=c++17 -fPIC -Wno-unused-parameter ${EXTRA[*]}"
 pids=()
-for f in flatmat gen errors flat_debug flat_io capi fitch_capi epp_capi epp_host assign_capi resolve_capi neighbors_capi; do
+for f in flatmat gen errors flat_debug flat_io capi fitch_capi epp_capi epp_host epp_sweep assign_capi resolve_capi neighbors_capi peaks_capi; do
   /opt/rocm/bin/hipcc $FLAGS -c $SRC/$f.cpp -o $OUT/$f.o & pids+=($!)
 done
 for f in $(cd $SRC && ls *.hip | sed 's/\.hip$//'); do

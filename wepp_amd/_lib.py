@@ -145,6 +145,18 @@ class NeighborsOutC(ctypes.Structure):
                 ("nbr_capacity", ctypes.c_uint64), ("top", ctypes.c_void_p), ("n_region", ctypes.c_void_p)]
 
 
+class PeaksParamsC(ctypes.Structure):
+    _fields_ = [("top_n", ctypes.c_uint32), ("max_peaks", ctypes.c_uint32), ("peak_radius", ctypes.c_uint32),
+                ("score_epsilon", ctypes.c_double)]
+
+
+class PeaksOutC(ctypes.Structure):
+    _fields_ = [("n_peaks", ctypes.c_void_p), ("n_steps", ctypes.c_void_p), ("n_remaining", ctypes.c_void_p),
+                ("peaks", ctypes.c_void_p), ("peak_step", ctypes.c_void_p), ("peak_reads", ctypes.c_void_p),
+                ("peak_degree", ctypes.c_void_p), ("peak_score", ctypes.c_void_p), ("removed_step", ctypes.c_void_p),
+                ("removed_peak", ctypes.c_void_p), ("mapped", ctypes.c_void_p), ("score_left", ctypes.c_void_p)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -204,6 +216,9 @@ _SIGS = {
                                           ctypes.POINTER(NeighborsOutC)]),
     "wepp_epp_distances": (ctypes.c_int, [_V, ctypes.c_uint32, _V, ctypes.c_int, _V]),
     "wepp_epp_neighbors_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
+    "wepp_epp_peaks": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.POINTER(PeaksParamsC), _V,
+                                      ctypes.POINTER(EppOutC), ctypes.POINTER(PeaksOutC)]),
+    "wepp_epp_peaks_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 5),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

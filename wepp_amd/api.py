@@ -651,6 +651,50 @@ class Mat:
         n = int(off[K])
         return dict(nbr_off=off, nbr_node=node[:n], nbr_dist=dist[:n], top=top[:K], n_region=nreg[:K])
 
+    def epp_peaks(self, reads, genome_size, top_n=10, max_peaks=300, peak_radius=2, score_epsilon=1e-9, tie_rank=None,
+                  want_map=False, want_scores=True):
+        """wepp_epp_peaks: the peak-removal loop of wepp_filter behind its own wepp_epp_map.  Returns peaks /
+        peak_step / peak_reads / peak_degree / peak_score in selection order, n_steps, n_remaining, removed_step /
+        removed_peak per read (-1 / 0xFFFFFFFF: the read remains), mapped per haplotype, score_left (want_scores) and,
+        with want_map, `map`: what Mat.epp_map returns for the same reads.  tie_rank: a uint32 per haplotype, the
+        place among haplotypes whose full scores tie (None: arena order)."""
+        R, n = reads.n_reads, self.n_nodes
+        cnt = np.zeros(3, np.uint32)
+        peaks = np.zeros(max_peaks, np.uint32); pstep = np.zeros(max_peaks, np.uint32); preads = np.zeros(max_peaks, np.uint32)
+        pdeg = np.zeros(max_peaks, np.int64); pscore = np.zeros(max_peaks, np.float64)
+        rstep = np.zeros(max(R, 1), np.int32); rpeak = np.zeros(max(R, 1), np.uint32)
+        mapped = np.zeros(n, np.uint8)
+        left = np.zeros(n, np.float64) if want_scores else None
+        rank = None if tie_rank is None else np.ascontiguousarray(tie_rank, dtype=np.uint32)
+        if rank is not None and rank.size != n:
+            raise ValueError("tie_rank holds one entry per haplotype")
+        rw = reads.read_word if reads.read_word.size else np.zeros(1, np.uint32)
+        rd = _lib.EppReadsC(R, _ptr(reads.read_off).value, _ptr(rw).value, _ptr(reads.start).value,
+                            _ptr(reads.end).value, _ptr(reads.degree).value)
+        par = _lib.PeaksParamsC(int(top_n), int(max_peaks), int(peak_radius), float(score_epsilon))
+        o = _lib.PeaksOutC(cnt.ctypes.data, cnt.ctypes.data + 4, cnt.ctypes.data + 8, _ptr(peaks).value if max_peaks else None,
+                           _ptr(pstep).value if max_peaks else None, _ptr(preads).value if max_peaks else None,
+                           _ptr(pdeg).value if max_peaks else None, _ptr(pscore).value if max_peaks else None,
+                           _ptr(rstep).value, _ptr(rpeak).value, _ptr(mapped).value, _ptr(left).value if want_scores else None)
+        mo = m = None
+        if want_map:
+            cap = 2048 * max(R, 1)
+            m = dict(mp=np.zeros(max(R, 1), np.int32), mult=np.zeros(max(R, 1), np.uint32), score=np.zeros(n, np.float64),
+                     counts=np.zeros((n, 50), np.int32), div=np.zeros(n, np.float64), eoff=np.zeros(R + 1, np.uint64),
+                     enodes=np.zeros(cap, np.uint32))
+            mo = _lib.EppOutC(_ptr(m["mp"]).value, _ptr(m["mult"]).value, _ptr(m["eoff"]).value, _ptr(m["enodes"]).value, cap,
+                              _ptr(m["score"]).value, _ptr(m["counts"]).value, _ptr(m["div"]).value)
+        check(lib.wepp_epp_peaks(self._h, ctypes.byref(rd), int(genome_size), ctypes.byref(par), _ptr(rank) if rank is not None else None,
+                                 ctypes.byref(mo) if mo is not None else None, ctypes.byref(o)))
+        k = int(cnt[0])
+        out = dict(n_peaks=k, n_steps=int(cnt[1]), n_remaining=int(cnt[2]), peaks=peaks[:k], peak_step=pstep[:k], peak_reads=preads[:k],
+                   peak_degree=pdeg[:k], peak_score=pscore[:k], removed_step=rstep[:R], removed_peak=rpeak[:R], mapped=mapped,
+                   score_left=left)
+        if want_map:
+            out["map"] = dict(max_parsimony=m["mp"][:R], multiplicity=m["mult"][:R], score=m["score"], counts=m["counts"],
+                              divergence=m["div"], epp_off=m["eoff"], epp_nodes=m["enodes"][: int(m["eoff"][R])])
+        return out
+
     def epp_distances(self, piv, form):
         """wepp_epp_distances: [len(piv), n_nodes] mutation distances between every pivot and every haplotype."""
         piv = np.ascontiguousarray(piv, dtype=np.uint32)
@@ -763,3 +807,10 @@ def epp_neighbors_last_timing():
     d = [ctypes.c_double() for _ in range(3)]
     check(lib.wepp_epp_neighbors_last_timing(*[ctypes.byref(x) for x in d]))
     return dict(tables_ms=d[0].value, field_ms=d[1].value, region_ms=d[2].value)
+
+
+def epp_peaks_last_timing():
+    """Wall time by phase (ms) of this thread's last Mat.epp_peaks call."""
+    d = [ctypes.c_double() for _ in range(5)]
+    check(lib.wepp_epp_peaks_last_timing(*[ctypes.byref(x) for x in d]))
+    return dict(map_ms=d[0].value, select_ms=d[1].value, hits_ms=d[2].value, remove_ms=d[3].value, clear_ms=d[4].value)

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "assign.hpp"
+#include "epp.hpp"
 #include "handle.hpp"
 
 namespace wepp {
@@ -84,6 +85,49 @@ struct DevReads {                      // a read batch on the device
 };
 int alloc_reads(DevPool& pool, uint32_t R, uint64_t W, DevReads* reads);   // the six blocks of R reads with W words: WEPP_OK or WEPP_ENOMEM
 int upload_reads(DevPool& pool, const wepp_epp_reads* rd, const std::vector<uint32_t>& order, hipStream_t stream, DevReads* reads);   // ... filled with rd (n_reads > 0) in `order`
+
+// ---- the map's sweep as a routine (epp_sweep.cpp: it launches the kernels of epp_kernels.hip, which the emulated
+// library of tests/epp_emu.py does not have, so it stays out of epp_host.cpp) ------------------------------------------
+// A planned sweep of the reads order[0 .. n) between its two passes: wepp_epp_map runs it over a whole batch,
+// wepp_epp_peaks once more over every subset of reads it takes out of the scores.
+struct EppSweep {
+    EppSweepArgs a{};                  // groups, streams, partial rows; best / mult / delta_fx per place in `order`
+    uint32_t rpl = 1, lds_bytes = 0, tiles_per_group = 1;
+    uint64_t events_swept = 0, stream_events = 0;
+};
+// Plans tiles, groups and jobs for the reads order[..] (in window order; `reads` holds the batch on the device with
+// reads.order = the same list), cuts the window streams, runs pass 1 and the combine: a.best / a.mult / a.delta_fx are
+// on the device afterwards, delta_fx = round(node_score * fx_scale).  `begin` / `selected` (may be null) are recorded
+// before the selection and behind it.  WEPP_OK, WEPP_ELIMIT, WEPP_ENOMEM or WEPP_EDEVICE.
+int epp_sweep_pass1(wepp_mat_t* mat, DevPool& pool, const wepp_epp_reads* rd, const std::vector<uint32_t>& order, const DevReads& reads,
+                    uint32_t genome_size, double fx_scale, hipStream_t stream, hipEvent_t begin, hipEvent_t selected, EppSweep* sw);
+// Pass 2: every node range on which a read attains its minimum receives +delta_fx .. -delta_fx of that read in
+// diff_score[N + 1] (delta_fx per place in `order`; null = the combine's own), its degree in diff_cnt (or null), and
+// the nodes go to epp_nodes for the reads r with epp_base[r] != ~0 (epp_base is indexed by read).
+int epp_sweep_pass2(const EppSweep& sw, const long long* delta_fx, const uint64_t* epp_base, uint32_t* epp_nodes,
+                    unsigned long long* diff_score, int* diff_cnt, hipStream_t stream);
+
+// What wepp_epp_map leaves on the device (in the blocks of the caller's pool) for a caller that goes on from it.
+struct EppMapState {
+    std::vector<uint32_t> order;       // place in window order -> read
+    DevReads reads;
+    EppSweep sweep;                    // sweep.a.best / mult / delta_fx: P, M and q per place in `order`
+    double fx_scale = 1.0;
+    unsigned long long* diff_score = nullptr;   // [N + 1] the fixed-point difference array of the scores
+    double* score = nullptr;           // [N]
+    double* divergence = nullptr;      // [N], when asked for
+    void* scan_scratch = nullptr;      // epp_finish_scratch_bytes(N)
+    float select_ms = 0, sweep1_ms = 0, sweep2_ms = 0, finish_ms = 0;
+    uint32_t groups = 0, jobs = 0;
+};
+// The body of wepp_epp_map behind its argument checks (n_reads > 0, reads validated, total_degree their degrees' sum):
+// every output of `out` is delivered as wepp_epp_map documents it.  want_divergence computes st->divergence even when
+// out->hap_divergence is null.
+int epp_map_run(wepp_mat_t* mat, DevPool& pool, const wepp_epp_reads* rd, uint32_t genome_size, uint32_t max_cached_epp,
+                long long total_degree, wepp_epp_out* out, bool want_divergence, EppMapState* st);
+
+// wepp_epp_neighbors' per-handle preparation (dfs_end on the device, the forced pass size), made by the first call
+int nbr_prepare_handle(wepp_mat_t* mat);
 
 // The argument checks of the entry points that take a selection, in the order they are made: what can be said about the
 // selection without the handle; the handle, the range of the indices and the read arrays; then (after the entry point has looked at its

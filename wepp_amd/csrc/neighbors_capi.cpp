@@ -164,6 +164,8 @@ int run(wepp_mat_t* mat, uint32_t K, const uint32_t* piv, uint32_t radius, int f
 
 }  // namespace
 
+int wepp::nbr_prepare_handle(wepp_mat_t* mat) { return prepare_handle(mat); }   // (wepp_epp_peaks runs the field kernels itself)
+
 extern "C" int wepp_epp_neighbors_last_timing(double* tables_ms, double* field_ms, double* region_ms) {
     if (tables_ms) *tables_ms = g_last.tables_ms;
     if (field_ms) *field_ms = g_last.field_ms;

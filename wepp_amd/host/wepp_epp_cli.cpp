@@ -2,12 +2,13 @@
 // wepp_filter::cartesian_map, on files: MAT .pb[.gz] + reads .pb (sam.proto, as written by
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
 //   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE [--resolve RESIDUAL]]
-//            [--neighbors FILE [--radius R] [--max-neighbors L]]
+//            [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
 // --assign FILE: FILE names the selected haplotypes, one identifier of a condensed node per line (anything after a
-// tab or comma is ignored; an unknown or repeated identifier is an error).  After the map the reads are assigned to
+// tab or comma is ignored; an unknown or repeated identifier is an error).  A line that is no identifier but a number
+// below the number of haplotypes is an arena index (the pre-order of the condensed tree): peaks.txt of --peaks.  After the map the reads are assigned to
 // their nearest selected haplotypes (arena::dump_read2haplotype_mapping, arena.cpp:590-696, without the SAM files):
 //         <outdir>/haplotype_reads.csv     one row per selected haplotype that has a read, in the order of FILE:
 //                                          id,name,name,... -- the names reverse_merge (the reads file's column table) lists
@@ -33,6 +34,12 @@
 //         <outdir>/haplotype_neighbors.csv one row per selected haplotype, in the order of FILE: id,id:distance,... --
 //                                          its neighbours (itself among them) in rank order with their distances.
 //         <outdir>/next_selection.txt      the union in rank order, one identifier per line: the next FILE.
+// --peaks [--top-n T] [--max-peaks P] [--peak-radius Q] (defaults 10, 300, 2: config.hpp:19-22): the whole of
+// wepp_filter::filter (initial_filter.cpp:455-506) -- the map, the peak-removal loop and the five expansion rounds:
+//         <outdir>/peaks.txt               the selection in the checkpoint format of pipeline::save: one arena index per
+//                                          line, the peaks (ascending) then the neighbours (ascending).  --assign reads it.
+//         <outdir>/peak_reads.csv          one row per peak in the order it was chosen: id,reads,degree,step -- the reads
+//                                          the loop removed for it, the sum of their degrees, the step that chose it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -45,7 +52,8 @@
 int main(int argc, char** argv) {
     std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, neighbors_f, outdir = ".";
     int device = 0, radius = 2, max_neighbors = 500;       // config.hpp:24-25
-    bool dump = false;
+    peaks_params peak_par;
+    bool dump = false, want_peaks = false;
     for (int i = 1; i < argc; i++) {
         auto need = [&](const char* flag) -> const char* {
             if (i + 1 >= argc) { fprintf(stderr, "ERROR: %s needs a value\n", flag); exit(1); }
@@ -63,10 +71,14 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--neighbors")) neighbors_f = need("--neighbors");
         else if (!strcmp(argv[i], "--radius")) radius = atoi(need("--radius"));
         else if (!strcmp(argv[i], "--max-neighbors")) max_neighbors = atoi(need("--max-neighbors"));
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]]\n"); return 1; }
+        else if (!strcmp(argv[i], "--peaks")) want_peaks = true;
+        else if (!strcmp(argv[i], "--top-n")) peak_par.top_n = atoi(need("--top-n"));
+        else if (!strcmp(argv[i], "--max-peaks")) peak_par.max_peaks = atoi(need("--max-peaks"));
+        else if (!strcmp(argv[i], "--peak-radius")) peak_par.peak_radius = atoi(need("--peak-radius"));
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]\n");
         return 1;
     }
     if (!resolve_f.empty() && assign_f.empty()) {
@@ -75,6 +87,10 @@ int main(int argc, char** argv) {
     }
     if (radius < 0 || max_neighbors < 1) {
         fprintf(stderr, "ERROR: --radius must be at least 0 and --max-neighbors at least 1\n");
+        return 1;
+    }
+    if (peak_par.top_n < 1 || peak_par.max_peaks < 1 || peak_par.peak_radius < 0) {
+        fprintf(stderr, "ERROR: --top-n and --max-peaks must be at least 1 and --peak-radius at least 0\n");
         return 1;
     }
     try {
@@ -107,15 +123,21 @@ int main(int argc, char** argv) {
         auto read_selection = [&](const std::string& file, std::vector<MAT::Node*>& nodes, std::vector<std::string>& ids) -> bool {
             std::ifstream in(file);
             if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", file.c_str()); return false; }
-            std::unordered_set<std::string> seen;
+            std::unordered_set<MAT::Node*> seen;
+            std::vector<MAT::Node*> arena;                                    // filled when a line is an arena index
             std::string line;
             while (std::getline(in, line)) {
                 if (!line.empty() && line.back() == '\r') line.pop_back();
                 line = line.substr(0, line.find_first_of("\t,"));
                 if (line.empty()) continue;
                 MAT::Node* n = condensed.get_node(line);
+                if (!n && line.size() <= 9 && line.find_first_not_of("0123456789") == std::string::npos) {
+                    if (arena.empty()) arena = condensed.depth_first_expansion();   // arena::from_mat, arena.cpp:3-55
+                    const size_t k = (size_t)atol(line.c_str());
+                    if (k < arena.size()) { n = arena[k]; line = n->identifier; }
+                }
                 if (!n) { fprintf(stderr, "ERROR: %s: %s is not a haplotype of the condensed tree\n", file.c_str(), line.c_str()); return false; }
-                if (!seen.insert(line).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", file.c_str(), line.c_str()); return false; }
+                if (!seen.insert(n).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", file.c_str(), line.c_str()); return false; }
                 nodes.push_back(n);
                 ids.push_back(line);
             }
@@ -129,8 +151,17 @@ int main(int argc, char** argv) {
         // so is the residual list
         std::vector<residual_mutation> residual;
         if (!resolve_f.empty()) residual = load_residual_mutations(resolve_f, reference);
-        cartesian_map_result res;
-        if (cartesian_map(condensed, reads, reference.size(), res, device) != 0) return 1;
+        filter_result filtered;
+        cartesian_map_result own_map;
+        if (want_peaks) {
+            if (wepp_filter_filter(condensed, reads, reference.size(), mappings, peak_par, filtered, device) != 0) return 1;
+        } else if (cartesian_map(condensed, reads, reference.size(), own_map, device) != 0) return 1;
+        cartesian_map_result& res = want_peaks ? filtered.loop.map : own_map;
+        {
+            // an arena index in a selection file means a place in this order
+            std::vector<MAT::Node*> pre = condensed.depth_first_expansion();
+            if (pre != res.haplotypes) { fprintf(stderr, "ERROR: the arena order is not the pre-order of the condensed tree\n"); return 1; }
+        }
         FILE* f = fopen((outdir + "/haplotype_scores.tsv").c_str(), "w");
         if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
         fprintf(f, "haplotype\tscore\tdist_divergence\tsources\n");
@@ -145,6 +176,20 @@ int main(int argc, char** argv) {
             fprintf(f, "%s\t%d\t%d\t%d\t%d\t%d\n", reads[r].read.c_str(), reads[r].start, reads[r].end, reads[r].degree,
                     res.max_parismony[r], res.parsimony_multiplicity[r]);
         fclose(f);
+        if (want_peaks) {
+            const peaks_result& pk = filtered.loop;
+            f = fopen((outdir + "/peaks.txt").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (int h : filtered.selection) fprintf(f, "%d\n", h);
+            fclose(f);
+            f = fopen((outdir + "/peak_reads.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t k = 0; k < pk.peaks.size(); k++)
+                fprintf(f, "%s,%d,%lld,%d\n", res.haplotypes[(size_t)pk.peaks[k]]->identifier.c_str(), pk.peak_reads[k], pk.peak_degree[k], pk.peak_step[k]);
+            fclose(f);
+            fprintf(stderr, "%zu peaks in %d steps, %d reads remain, %zu neighbours (round %d)\n", pk.peaks.size(), pk.n_steps, pk.n_remaining,
+                    filtered.neighbors.size(), filtered.round);
+        }
         if (!selected.empty()) {
             read2haplotype_result asg;
             if (read2haplotype_mapping(condensed, reads, reference.size(), selected, asg, device) != 0) return 1;

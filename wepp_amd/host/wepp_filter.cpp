@@ -5,6 +5,7 @@
 #include <cctype>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <fstream>
 #include <iterator>
 #include <sstream>
@@ -477,5 +478,134 @@ int closest_neighbors(MAT::Tree& condensed, const std::vector<MAT::Node*>& selec
         for (int h : out.neighbors[k]) out.distance[k].push_back(dist_of[h]);
     }
     out.next_selection = add_neighbors(out.neighbors, keys);
+    return 0;
+}
+
+namespace {
+
+// the loop on an open handle
+int run_peaks(wepp_mat_t* mat, const std::vector<MAT::Node*>& bfs, const std::vector<raw_read>& reads, size_t genome_size,
+              const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings, const peaks_params& params,
+              peaks_result& out) {
+    const size_t N = bfs.size(), R = reads.size();
+    if (params.top_n < 1 || params.max_peaks < 1 || params.peak_radius < 0) {
+        fprintf(stderr, "ERROR: top_n and max_peaks must be at least 1 and peak_radius at least 0\n");
+        return 1;
+    }
+    std::vector<uint32_t> order(N);
+    if (wepp_mat_dfs_order(mat, order.data()) != WEPP_OK) {
+        fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+        return 1;
+    }
+    cartesian_map_result& map = out.map;
+    map.haplotypes.resize(N);
+    for (size_t k = 0; k < N; k++) map.haplotypes[k] = bfs[order[k]];
+    // score_comparator's last two criteria (arena.hpp:24-29) as a rank: more leaves first, then the larger identifier
+    const std::vector<size_t> leaves = haplotype_leaf_counts(map.haplotypes, node_mappings);
+    std::vector<uint32_t> by_rank(N), tie_rank(N);
+    for (size_t k = 0; k < N; k++) by_rank[k] = (uint32_t)k;
+    std::sort(by_rank.begin(), by_rank.end(), [&](uint32_t a, uint32_t b) {
+        if (leaves[a] != leaves[b]) return leaves[a] > leaves[b];
+        return map.haplotypes[a]->identifier > map.haplotypes[b]->identifier;
+    });
+    for (size_t k = 0; k < N; k++) tie_rank[by_rank[k]] = (uint32_t)k;
+
+    packed_reads pr(reads);
+    wepp_epp_reads in = pr.view();
+    const uint32_t P = (uint32_t)params.max_peaks;
+    std::vector<int32_t> pars(R), counts(N * NUM_RANGE_BINS), rstep(R);
+    std::vector<uint32_t> mult(R), peaks(P), pstep(P), preads(P), rpeak(R);
+    std::vector<int64_t> pdeg(P);
+    std::vector<uint8_t> mapped(N);
+    uint32_t n_peaks = 0, n_steps = 0, n_remaining = 0;
+    map.score.assign(N, 0.0);
+    map.dist_divergence.assign(N, 0.0);
+    out.peak_score.assign(P, 0.0);
+    wepp_epp_out mo{pars.data(), mult.data(), nullptr, nullptr, 0, map.score.data(), counts.data(), map.dist_divergence.data()};
+    wepp_peaks_params pp{(uint32_t)params.top_n, P, (uint32_t)params.peak_radius, SCORE_EPSILON};
+    wepp_peaks_out po{&n_peaks, &n_steps, &n_remaining, peaks.data(), pstep.data(), preads.data(), pdeg.data(), out.peak_score.data(),
+                      rstep.data(), rpeak.data(), mapped.data(), nullptr};
+    if (wepp_epp_peaks(mat, &in, (uint32_t)genome_size, &pp, tie_rank.data(), &mo, &po) != WEPP_OK) {
+        fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+        return 1;
+    }
+    map.mapped_read_counts.resize(N);
+    for (size_t k = 0; k < N; k++) std::copy_n(&counts[k * NUM_RANGE_BINS], NUM_RANGE_BINS, map.mapped_read_counts[k].begin());
+    map.max_parismony.assign(pars.begin(), pars.end());
+    map.parsimony_multiplicity.assign(mult.begin(), mult.end());
+    map.epp_positions_cache.assign(R, {});
+    out.keys = haplotype_keys(map, leaves);
+    out.peaks.assign(peaks.begin(), peaks.begin() + n_peaks);
+    out.peak_step.assign(pstep.begin(), pstep.begin() + n_peaks);
+    out.peak_reads.assign(preads.begin(), preads.begin() + n_peaks);
+    out.peak_degree.assign(pdeg.begin(), pdeg.begin() + n_peaks);
+    out.peak_score.resize(n_peaks);
+    out.removed_step.assign(rstep.begin(), rstep.end());
+    out.removed_peak.resize(R);
+    for (size_t r = 0; r < R; r++) out.removed_peak[r] = rpeak[r] == 0xFFFFFFFFu ? -1 : (int)rpeak[r];
+    out.mapped.assign(mapped.begin(), mapped.end());
+    out.n_steps = (int)n_steps;
+    out.n_remaining = (int)n_remaining;
+    return 0;
+}
+
+}  // namespace
+
+int wepp_filter_peaks(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                      const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings, const peaks_params& params,
+                      peaks_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    const int rc = run_peaks(mat, bfs, reads, genome_size, node_mappings, params, out);
+    wepp_mat_destroy(mat);
+    return rc;
+}
+
+int wepp_filter_filter(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                       const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings, const peaks_params& params,
+                       filter_result& out, int device) {
+    std::vector<MAT::Node*> bfs;
+    wepp_mat_t* mat = nullptr;
+    if (make_handle(condensed, device, bfs, &mat) != 0) return 1;
+    if (run_peaks(mat, bfs, reads, genome_size, node_mappings, params, out.loop) != 0) {
+        wepp_mat_destroy(mat);
+        return 1;
+    }
+    const std::vector<int>& peaks = out.loop.peaks;
+    const size_t K = peaks.size();
+    out.neighbors.clear();
+    out.round = -1;
+    std::vector<uint32_t> piv(peaks.begin(), peaks.end());
+    std::vector<uint64_t> off(K + 1, 0);
+    std::vector<uint32_t> node(std::max<size_t>(K, 1) * 64);
+    std::vector<int32_t> dist(node.size());
+    for (int k = 0; k < 5 && K; k++) {                                         // :474
+        const uint32_t radius = (uint32_t)(params.peak_radius + k);
+        wepp_neighbors_out o{off.data(), node.data(), dist.data(), node.size(), nullptr, nullptr};
+        int rc = wepp_epp_neighbors(mat, (uint32_t)K, piv.data(), radius, WEPP_NBR_FROM_PIVOT, nullptr, &o);
+        if (rc == WEPP_ELIMIT && off[K] > node.size()) {
+            node.assign((size_t)off[K], 0);
+            dist.assign((size_t)off[K], 0);
+            o.nbr_node = node.data(); o.nbr_dist = dist.data(); o.nbr_capacity = node.size();
+            rc = wepp_epp_neighbors(mat, (uint32_t)K, piv.data(), radius, WEPP_NBR_FROM_PIVOT, nullptr, &o);
+        }
+        if (rc != WEPP_OK) {
+            fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+            wepp_mat_destroy(mat);
+            return 1;
+        }
+        std::vector<std::vector<int>> regions(K);
+        for (size_t j = 0; j < K; j++) regions[j].assign(node.begin() + (long)off[j], node.begin() + (long)off[j + 1]);
+        std::vector<int> curr = expand_peaks(peaks, regions, out.loop.keys, MAX_NEIGHBORS_WEPP);
+        if (std::abs(FREYJA_PEAKS_LIMIT - (int)(curr.size() + K)) < std::abs(FREYJA_PEAKS_LIMIT - (int)(out.neighbors.size() + K))) {   // :499
+            out.neighbors.swap(curr);
+            out.round = k;
+        }
+    }
+    wepp_mat_destroy(mat);
+    out.selection.assign(peaks.begin(), peaks.end());
+    std::sort(out.selection.begin(), out.selection.end());                     // (std::set<haplotype*>: arena order)
+    out.selection.insert(out.selection.end(), out.neighbors.begin(), out.neighbors.end());
     return 0;
 }

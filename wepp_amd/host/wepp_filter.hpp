@@ -3,7 +3,8 @@
 // loader, read masking, the condensed tree, the call itself on top of wepp_epp_map, the
 // read loop of arena::dump_read2haplotype_mapping on top of wepp_epp_assign,
 // arena::resolve_unaccounted_mutations on top of wepp_epp_resolve, and arena::closest_neighbors with the
-// "add neighbors" step of post_filter::iterative_filter on top of wepp_epp_neighbors.
+// "add neighbors" step of post_filter::iterative_filter on top of wepp_epp_neighbors, and wepp_filter::filter itself:
+// the peak loop on top of wepp_epp_peaks and the five expansion rounds on top of wepp_epp_neighbors.
 // Same names and argument meaning as the reference; errors throw MAT::mat_error.
 #pragma once
 #include <array>
@@ -117,3 +118,39 @@ struct neighbors_result {
 // after printing the error.
 int closest_neighbors(MAT::Tree& condensed, const std::vector<MAT::Node*>& selected, const std::vector<haplotype_key>& keys,
                       int max_radius, int num_limit, neighbors_result& out, int device = 0);
+
+// ---- wepp_filter::filter (initial_filter.cpp:455-506) ------------------------------------------------------------------
+static constexpr int TOP_N = 10, MAX_PEAKS = 300, MAX_PEAK_PEAK_MUTATION = 2;      // src/WEPP/config.hpp:19-22
+static constexpr int MAX_NEIGHBORS_WEPP = 50, FREYJA_PEAKS_LIMIT = 5000;           // config.hpp:20,23
+struct peaks_params { int top_n = TOP_N, max_peaks = MAX_PEAKS, peak_radius = MAX_PEAK_PEAK_MUTATION; };
+
+// cartesian_map and `while (!step(...))` (:465-469) in one device call (wepp_epp_peaks).  Haplotypes are arena indices.
+struct peaks_result {
+    cartesian_map_result map;                      // what the loop started from (epp_positions_cache is not filled)
+    std::vector<haplotype_key> keys;               // what score_comparator reads, with the ORIGINAL scores
+    std::vector<int> peaks, peak_step, peak_reads; // selection order; reads removed for the peak
+    std::vector<long long> peak_degree;            // ... and the sum of their degrees
+    std::vector<double> peak_score;                // full_score when chosen
+    std::vector<int> removed_step, removed_peak;   // per read: the step and the place in `peaks`, -1 for a read that remains
+    std::vector<char> mapped;                      // per haplotype
+    int n_steps = 0, n_remaining = 0;
+};
+// The order among haplotypes whose full scores tie is score_comparator's: more leaves first (haplotype_leaf_counts
+// over node_mappings), then the larger identifier.  Returns 0, or 1 after printing the error.
+int wepp_filter_peaks(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                      const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings, const peaks_params& params,
+                      peaks_result& out, int device = 0);
+
+// the whole of filter(): the loop, then the five expansion rounds (:473-504) -- per round k one wepp_epp_neighbors call
+// (radius peak_radius + k, pivot->mutation_distance(node), nothing skipped), expand_peaks (neighbor_rank.hpp) on the
+// original scores, and the round whose peaks + neighbours come closest to FREYJA_PEAKS_LIMIT is kept (the earlier one
+// of two equally close)
+struct filter_result {
+    peaks_result loop;
+    std::vector<int> neighbors;                    // ascending arena indices
+    int round = -1;                                // the round kept (-1: none added anything to an empty set)
+    std::vector<int> selection;                    // filter()'s return value: the peaks ascending, then the neighbours
+};
+int wepp_filter_filter(MAT::Tree& condensed, const std::vector<raw_read>& reads, size_t genome_size,
+                       const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings, const peaks_params& params,
+                       filter_result& out, int device = 0);
