@@ -669,6 +669,61 @@ int wepp_epp_peaks(wepp_mat_t *mat, const wepp_epp_reads *reads, uint32_t genome
  * the scores (the map's sweep over the subset); the regions that become mapped */
 int wepp_epp_peaks_last_timing(double *map_ms, double *select_ms, double *hits_ms, double *remove_ms, double *clear_ms);
 
+/* ---- aligned reads to merged reads (sam2PB without the parse) ---------------- *
+ * Replaces sam::build behind sam::add_reads (src/WEPP/sam2pb.cpp:262-275, 281-314, 456-470 with operator< / == of
+ * sam2pb.hpp:33-47) under the reference's constants USE_READ_CORRECTION, USE_COLUMN_MERGING,
+ * !MAP_TO_MAJORITY_INSTEAD_OF_N and SCORE_EPSILON = 1e-9.  No tree handle: the call runs on HIP device `device`.
+ * Input: `reference` = the genome_size characters of the reference as dataset::reference delivers them (ASCII, upper
+ * case); aligned read r starts at the 0-based site start[r] and holds the columns base[base_off[r] .. base_off[r+1]),
+ * one byte 0..5 = "ACGTN_" each (sam2pb.hpp:10).
+ *   1. freq[site * 6 + c] = the columns with character c at the site, c != N (the N column stays 0, '_' is counted).
+ *   2. total = the six columns' sum; a column with character c becomes N when min_depth > total, else when
+ *      min_af - (double)freq[c] / (double)total > 1e-9 (IEEE fp64 as written: total == 0 gives NaN, the comparison is
+ *      false and the column stays); then '_' becomes N.  (The table update of :316-328 feeds only dead code: not built.)
+ *   3. the reads are ordered by start, then length, then the corrected string in ASCII order (A < C < G < N < T);
+ *      reads equal in (start, string) merge into one whose degree is their number.
+ * Outputs (host buffers): freq (the RAW table of step 1; may be NULL); order[s] = the input read at place s of the
+ * order; n_merged; group_off[g] .. group_off[g + 1] = the places of merged read g (group_off holds n_reads + 1
+ * entries, n_merged + 1 are written); and the merged batch in the fields of wepp_epp_reads -- start = start + 1,
+ * end = start + length - 1, degree, and one word (wepp_pack_read_word, position 1-based, ref_nuc / mut_nuc the
+ * nucleotide masks of the two characters, 15 and is_missing for N) per column whose corrected character differs from
+ * the reference character: what load_reads_from_proto (:489-549) makes of the file sam::dump_proto writes.
+ * Departures from the reference: among equal reads the one earliest in the input leads the group (order lists the
+ * members of a group by ascending input index; the reference's unstable sort leaves both open).  Subsampling
+ * (:362-454, std::random_device) is not built: the caller limits the reads.
+ * A read_word buffer that is too small (word_capacity < read_off[n_merged]; 0 with read_word = NULL asks for exactly
+ * that) follows wepp_epp_map's protocol: EVERY other output is delivered, the words wait in the calling thread and
+ * the call returns WEPP_ELIMIT; wepp_sam_fetch_words collects them (and drops them) without recomputing.
+ * WEPP_EINVAL: a null argument, a base byte > 5, a read outside [0, genome_size), an empty read, base_off[0] != 0 or
+ * offsets that do not ascend.  WEPP_ELIMIT: genome_size > WEPP_MAX_POSITION (the words' 20-bit positions),
+ * n_reads >= 2^31, 2^32 or more words in the merged reads.  n_reads == 0: WEPP_OK, n_merged = 0, freq zeroed.
+ * The pile-up reads every read's window once per tile of 2048 sites: the cost grows with genome_size / 2048. */
+typedef struct {
+    uint32_t n_reads;
+    const uint32_t *start;      /* [n_reads] 0-based site of the first column */
+    const uint64_t *base_off;   /* [n_reads + 1] */
+    const uint8_t *base;        /* [base_off[n_reads]] 0..5 = ACGTN_ */
+} wepp_sam_reads;
+typedef struct { double min_af; uint32_t min_depth; } wepp_sam_params;   /* dataset::min_af (a float, widened), min_depth */
+typedef struct {
+    int32_t *freq;              /* [genome_size * 6] or NULL */
+    uint32_t *n_merged;         /* [1] */
+    uint32_t *order;            /* [n_reads] */
+    uint32_t *group_off;        /* [n_reads + 1] */
+    uint32_t *read_off;         /* [n_reads + 1]; the five fields of wepp_epp_reads, n_merged reads */
+    uint32_t *read_word;        /* [word_capacity] or NULL */
+    int32_t *start;             /* [n_reads] */
+    int32_t *end;               /* [n_reads] */
+    int32_t *degree;            /* [n_reads] */
+    uint64_t word_capacity;
+} wepp_sam_out;
+int wepp_sam_build(int device, const uint8_t *reference, uint32_t genome_size, const wepp_sam_reads *reads,
+                   const wepp_sam_params *params, wepp_sam_out *out);
+int wepp_sam_fetch_words(uint32_t *read_word, uint64_t capacity);
+/* device time of the calling thread's last wepp_sam_build by phase (HIP events, ms): the pile-up with the keep table;
+ * the correction (word counts, their scan, the words); the sort; the merge (flags, scans, the merged batch) */
+int wepp_sam_last_timing(double *pileup_ms, double *correct_ms, double *sort_ms, double *merge_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

@@ -157,6 +157,20 @@ class PeaksOutC(ctypes.Structure):
                 ("removed_peak", ctypes.c_void_p), ("mapped", ctypes.c_void_p), ("score_left", ctypes.c_void_p)]
 
 
+class SamReadsC(ctypes.Structure):
+    _fields_ = [("n_reads", ctypes.c_uint32), ("start", ctypes.c_void_p), ("base_off", ctypes.c_void_p), ("base", ctypes.c_void_p)]
+
+
+class SamParamsC(ctypes.Structure):
+    _fields_ = [("min_af", ctypes.c_double), ("min_depth", ctypes.c_uint32)]
+
+
+class SamOutC(ctypes.Structure):
+    _fields_ = [("freq", ctypes.c_void_p), ("n_merged", ctypes.c_void_p), ("order", ctypes.c_void_p), ("group_off", ctypes.c_void_p),
+                ("read_off", ctypes.c_void_p), ("read_word", ctypes.c_void_p), ("start", ctypes.c_void_p), ("end", ctypes.c_void_p),
+                ("degree", ctypes.c_void_p), ("word_capacity", ctypes.c_uint64)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -219,6 +233,10 @@ _SIGS = {
     "wepp_epp_peaks": (ctypes.c_int, [_V, ctypes.POINTER(EppReadsC), ctypes.c_uint32, ctypes.POINTER(PeaksParamsC), _V,
                                       ctypes.POINTER(EppOutC), ctypes.POINTER(PeaksOutC)]),
     "wepp_epp_peaks_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 5),
+    "wepp_sam_build": (ctypes.c_int, [ctypes.c_int, _V, ctypes.c_uint32, ctypes.POINTER(SamReadsC), ctypes.POINTER(SamParamsC),
+                                      ctypes.POINTER(SamOutC)]),
+    "wepp_sam_fetch_words": (ctypes.c_int, [_V, ctypes.c_uint64]),
+    "wepp_sam_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

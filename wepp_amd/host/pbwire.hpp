@@ -24,6 +24,33 @@ inline std::string slurp(std::string const& filename, const char* what) {
     return data;
 }
 
+// the lines of a text file, one at a time, plain or .gz alike (a line's '\n' is dropped, a '\r' before it is kept)
+struct Lines {
+    gzFile f;
+    std::string filename, what;
+    Lines(std::string const& name, const char* w) : f(gzopen(name.c_str(), "rb")), filename(name), what(w) {
+        if (!f) throw mat_error("ERROR: Could not open the " + what + " file: " + filename + "!");
+        gzbuffer(f, 1 << 18);
+    }
+    Lines(const Lines&) = delete;
+    Lines& operator=(const Lines&) = delete;
+    ~Lines() { gzclose(f); }
+    bool next(std::string& line) {
+        line.clear();
+        char buf[1 << 12];
+        bool any = false;
+        while (gzgets(f, buf, sizeof buf)) {
+            any = true;
+            line += buf;
+            if (!line.empty() && line.back() == '\n') { line.pop_back(); return true; }
+        }
+        int err = 0;
+        gzerror(f, &err);
+        if (err != Z_OK && err != Z_STREAM_END) throw mat_error("ERROR: Could not read the " + what + " file: " + filename + "!");
+        return any;
+    }
+};
+
 struct Wire {
     const uint8_t* p;
     const uint8_t* end;

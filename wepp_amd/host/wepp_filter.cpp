@@ -102,21 +102,51 @@ std::vector<raw_read> load_reads_from_proto(std::string const& reference, std::s
     return reads;
 }
 
+static void put_read_info(std::string& out, sam_read_record const& r) {
+    std::string m;
+    pbwire::put_len(m, 1, r.name);
+    pbwire::put_varint(m, (3u << 3) | 0);
+    pbwire::put_varint(m, (uint64_t)(int64_t)r.start_idx);
+    pbwire::put_varint(m, (5u << 3) | 0);
+    pbwire::put_varint(m, (uint64_t)(int64_t)r.degree);
+    pbwire::put_len(m, 6, r.content);
+    pbwire::put_len(out, 1, m);
+}
+
 void dump_reads_proto(std::vector<sam_read_record> const& reads, std::string const& filename) {
     std::string out;
-    for (auto const& r : reads) {
-        std::string m;
-        pbwire::put_len(m, 1, r.name);
-        pbwire::put_varint(m, (3u << 3) | 0);
-        pbwire::put_varint(m, (uint64_t)(int64_t)r.start_idx);
-        pbwire::put_varint(m, (5u << 3) | 0);
-        pbwire::put_varint(m, (uint64_t)(int64_t)r.degree);
-        pbwire::put_len(m, 6, r.content);
-        pbwire::put_len(out, 1, m);
-    }
+    for (auto const& r : reads) put_read_info(out, r);
     std::ofstream f(filename, std::ios::out | std::ios::binary);
     if (!f) throw mat_error("ERROR: Could not write the read protobuf: " + filename);
     f.write(out.data(), (std::streamsize)out.size());
+}
+
+void dump_reads_proto(std::vector<sam_read_record> const& reads, std::map<std::string, std::vector<std::string>> const& reverse_merge,
+                      std::string const& filename) {
+    const bool gz = filename.find(".gz") != std::string::npos;
+    const std::string fail = "ERROR: Could not write the read protobuf: " + filename;
+    gzFile zf = nullptr;
+    std::ofstream f;
+    if (gz) { zf = gzopen(filename.c_str(), "wb"); if (!zf) throw mat_error(fail); }
+    else { f.open(filename, std::ios::out | std::ios::binary); if (!f) throw mat_error(fail); }
+    std::string out;
+    auto flush = [&](bool all) {                        // the message leaves in pieces: it is as large as the reads
+        if (!all && out.size() < (1u << 22)) return;
+        if (gz) { if (!out.empty() && gzwrite(zf, out.data(), (unsigned)out.size()) != (int)out.size()) { gzclose(zf); throw mat_error(fail); } }
+        else f.write(out.data(), (std::streamsize)out.size());
+        out.clear();
+    };
+    for (auto const& r : reads) { put_read_info(out, r); flush(false); }
+    for (auto const& kv : reverse_merge) {
+        std::string m;
+        pbwire::put_len(m, 1, kv.first);
+        for (auto const& name : kv.second) pbwire::put_len(m, 2, name);
+        pbwire::put_len(out, 2, m);
+        flush(false);
+    }
+    flush(true);
+    if (gz) { if (gzclose(zf) != Z_OK) throw mat_error(fail); }
+    else { f.close(); if (!f) throw mat_error(fail); }
 }
 
 void mask_reads(std::vector<raw_read>& reads, std::vector<int> const& masked_sites) {

@@ -8,6 +8,7 @@
 // Same names and argument meaning as the reference; errors throw MAT::mat_error.
 #pragma once
 #include <array>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <unordered_set>
@@ -42,6 +43,10 @@ std::vector<raw_read> load_reads_from_proto(std::string const& reference, std::s
 // reads given as (name, 1-based start, aligned content over ACGTN_, degree)
 struct sam_read_record { std::string name; int start_idx; std::string content; int degree; };
 void dump_reads_proto(std::vector<sam_read_record> const& reads, std::string const& filename);
+// ... with the reverse_columns table behind the reads (:122-129: one column_info per entry of reverse_merge, in the
+// order of its keys), gzip-compressed when the name holds ".gz" (:136)
+void dump_reads_proto(std::vector<sam_read_record> const& reads, std::map<std::string, std::vector<std::string>> const& reverse_merge,
+                      std::string const& filename);
 
 // arena::arena, arena.hpp:58-72: mutations at masked sites are removed from the reads
 void mask_reads(std::vector<raw_read>& reads, std::vector<int> const& masked_sites);
