@@ -487,7 +487,7 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
 // handle:
 //   - the tree and everything built from it (read-only here);
 //   - the event ring (a slot claimed atomically);
-//   - the hints job_events, ww_by_jobs, expect_jobs8 and expect_lists (atomics; they choose how the next call cuts its work, never its results);
+//   - the hints job_events, ww_by_jobs, step_walkers, expect_jobs8 and expect_lists (atomics; they choose how the next call cuts its work, never its results);
 //   - the call statistics (stat_mu) and the device counters d_work (device atomics, summed over both lanes);
 //   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
 int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
@@ -691,7 +691,17 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             } else {
                 // (wwlist also takes the few walkers of 9 - 16 entries k_route moves there, TI_W16WAVE, whatever the hint
                 // ww_by_jobs says: k_step reads the lists' cursors, and is the plain blind walk when they are empty)
-                HIP_TRY(launch_step(mat->dev, stack8, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
+                // (the walkers by lane groups as wide as the most events one of them can hold: 8 lanes for the default
+                // limit, 16 while the handle lets up to WALK_MAX_EVENTS_BY_JOBS events walk plainly; a limit beyond
+                // (WEPP_WALK_MAX_EVENTS) and WEPP_STEP_GROUPS=0 keep them lane = read)
+                // A group pass costs a wave per 64 / G walkers where lane = read costs one per 64: a batch FULL of walkers
+                // (N-rich reads, bushy trees: several hundred thousand of a million) is cheaper lane = read, so the form
+                // goes by the walkers of the handle's previous call (step_walkers; a hint like ww_by_jobs: a call it
+                // misleads costs time, never a result)
+                const bool few = mat->step_walkers.load(std::memory_order_relaxed) <= STEP_GROUPS_MAX_WALKERS;
+                const uint32_t group = (!tun.step_groups || !few || walk_limit > 16u) ? 0u : walk_limit > 8u ? 16u : 8u;
+                if (tun.debug_plans) fprintf(stderr, "[step] walkers by groups of %u lanes (0: lane = read); plain walkers of the previous call: %u\n", group, mat->step_walkers.load(std::memory_order_relaxed));
+                HIP_TRY(launch_step(mat->dev, group, stack8, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
                                     d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream));
             }
             if (jobs8_blind) {
@@ -808,6 +818,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         const uint64_t scale = std::max<uint64_t>(1, ((uint64_t)n_reads + (1u << 20) - 1) >> 20);
         mat->ww_by_jobs.store((info[TI_WWCAND] > WW_CALL_MAX_SMALL * scale || info[TI_WWCAND + 1] > WW_CALL_MAX_BIG * scale) ? 1u : 0u, std::memory_order_relaxed);
     }
+    mat->step_walkers.store(info[TI_WCUR], std::memory_order_relaxed);      // (how the NEXT call's k_step places its plain walkers)
     bool late16[2] = {false, false}, late8 = false;
     if (blind_walks) {
         // the 8-entry job class when the hint did not expect it, and the hint of the next call

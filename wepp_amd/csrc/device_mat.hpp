@@ -211,10 +211,20 @@ hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_
 // (a wave each): ~2 150 workgroups.  With 1 024 the workgroups of the large reads took small ones behind them, on the
 // step's longest chain.
 constexpr uint32_t STEP_WAVE_WGS = 2560;
+// plain walkers of a call up to which the NEXT call's k_step places its walkers by lane groups (a wave per 64 / G of
+// them); beyond, lane = read (a wave per 64).  From the legs of bench.py --full (walkers of up to
+// 8 entries per call of a million reads, groups against the parent): 17 K, 38 K and 66 K (1, 2 entries a read and the
+// default batch) gain 2 - 6 %; 82 K and 83 K (the shard, 4 entries a read) are level; 94 K, 131 K and 134 K (5 % N, the
+// bushy tree, 8 entries a read) lose 4 - 17 %; 114 K (2 % N) gains, so the count is not all that matters -- the limit
+// sits under the level legs, 14 % above the default batches' 65.3 - 66.1 K and 20 % under the first losing leg, and the
+// legs between go lane = read, at the parent's time.
+constexpr uint32_t STEP_GROUPS_MAX_WALKERS = 75000;
 // the two common classes of a call in one launch sized BLIND (k_step): the plain walkers wlist[0 .. *wcount) of up to
 // WALK8_K entries as launch_walk_blind places them, and -- wwlist != nullptr -- the reads with many events as
-// launch_walk_wave places them (wwcount = its two cursors), in the first workgroups
-hipError_t launch_step(const DevMAT& m, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
+// launch_walk_wave places them (wwcount = its two cursors), in the first workgroups.  group = 8 / 16: the walkers by
+// groups of that many lanes a read (place_dev.hpp: group_read; no walker of the call holds more events than that);
+// 0: lane = read
+hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
                        const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
                        int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
 // a chunked class sized blind: jobs[0 .. *n_jobs) (k_route's table), partials into jb.part_*, then the combination over

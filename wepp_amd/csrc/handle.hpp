@@ -119,6 +119,7 @@ struct wepp_mat {
     static constexpr uint32_t kRing = 64;
     hipEvent_t ev0[kRing] = {}, ev1[kRing] = {};
     std::atomic<uint32_t> ww_by_jobs{0};  // the previous call held too many reads with 17 - 256 events for a wave each: this call cuts their walks into jobs (a hint, like job_events)
+    std::atomic<uint32_t> step_walkers{0};  // plain walkers of up to 8 entries of the previous call: above STEP_GROUPS_MAX_WALKERS this call's k_step places them lane = read, not by lane groups (a hint)
     std::atomic<uint32_t> expect_jobs8{0};  // the previous call held reads of the 8-entry job class: this call launches the class blind behind k_route, else from the counters (a hint too)
     std::atomic<uint32_t> expect_lists{0};  // the previous call held reads whose launches read the grouped read list: this call launches k_scatter blind behind the counters' copy, else only once the counters ask for it; bit 1: its last blind launch found no consumer (a hint too: capi.cpp)
     std::atomic<uint64_t> n_timed{0}; // placement calls since the last timing reset (a call claims its slot of the event ring when it starts)

@@ -278,6 +278,38 @@ struct PairAcc {
     int cb, cB;
     uint32_t T, stopA, stopB, fl;      // fl bit 0: an entry of the same node with a lower index; bit 1: ... of the same subtree end
 };
+// One pair of the all-pairs pass: what entry l = (nl, el) with the packed adjustments pl adds to the knowledge of the
+// entry (node, end); `lower`: l's index in the read is below the entry's own.  Differences wrap to huge values when the
+// cut lies in front of the start, so plain minima do.  The one statement of the arithmetic: the 64-lane pass (wave_read),
+// the group pass (group_read) and the CPU (tests/cxx/group_pass_emu.cpp) all call it.
+__host__ __device__ __forceinline__ uint32_t pair_min(uint32_t a, uint32_t b) { return a < b ? a : b; }
+__host__ __device__ __forceinline__ void pair_update(PairAcc& a, uint32_t node, uint32_t end, uint32_t nl, uint32_t el, uint32_t pl, bool lower) {
+    const int dl = (int)(pl & 0xFFu) - PK_BIAS;
+    const uint32_t nl1 = nl + 1u, span = el - nl1, sA = node + 1u, e2 = end << 1;
+    if (dl != 0) {
+        if (node - nl1 < span) a.cb += dl;
+        if (end - nl1 < span) a.cB += dl;
+    }
+    const bool same = nl == node;
+    a.T += same ? pl : 0u;
+    a.fl |= (lower && same ? 1u : 0u) | (lower && el == end ? 2u : 0u);
+    a.stopA = pair_min(a.stopA, pair_min(nl - sA, el - sA));
+    a.stopB = pair_min(a.stopB, pair_min((nl << 1) - e2, (el << 1) - 1u - e2));       // (entry nodes at e cut, ends behind e cut)
+}
+// the pass of a GROUP of G lanes (one read): entry `own` = (node, end) of a read of E <= G entries against all of them.
+// get(l, nl, el, pl) hands out entry l -- on the device an exchange that EVERY lane of the wave takes part in, whatever
+// its own group's E, so only the update is guarded.
+template <uint32_t G, typename Get>
+__host__ __device__ __forceinline__ PairAcc group_pairs(uint32_t node, uint32_t end, uint32_t own, uint32_t E, Get get) {
+    PairAcc a{0, 0, 0u, NONE, NONE, 0u};
+#pragma unroll
+    for (uint32_t ll = 0; ll < G; ll++) {
+        uint32_t nl, el, pl;
+        get(ll, nl, el, pl);
+        if (ll < E) pair_update(a, node, end, nl, el, pl, ll < own);
+    }
+    return a;
+}
 
 // ---- a read of more than 64 events: sort and scan instead of all pairs ----
 // Every field of PairAcc is a rank, a prefix sum or a successor query over the entries' node and end keys:
@@ -419,30 +451,15 @@ __device__ __forceinline__ void wave_read(const DevWalk& ix, const WcInfo& wi, u
             }
         }
     }
-    // ---- all pairs (R == 1): differences wrap to huge values when the cut lies in front of the start, so plain minima do
+    // ---- all pairs (R == 1): pair_update above, entry ll broadcast from its lane
     auto pairs = [&]() -> PairAcc {
         const uint32_t node = bnode[0], end = bend[0];
         PairAcc a{0, 0, 0u, NONE, NONE, 0u};
-        unsigned long long lower_same = 0ull, lower_end = 0ull;
-        const uint32_t sA = node + 1u, e2 = end << 1;
         for (uint32_t ll = 0; ll < E; ll++) {
             const uint32_t nl = (uint32_t)__builtin_amdgcn_readlane((int)bnode[0], (int)ll), el = (uint32_t)__builtin_amdgcn_readlane((int)bend[0], (int)ll);
             const uint32_t pl = (uint32_t)__builtin_amdgcn_readlane((int)bpk[0], (int)ll);
-            const int dl = (int)(pl & 0xFFu) - PK_BIAS;
-            const uint32_t nl1 = nl + 1u, span = el - nl1, nl2 = nl << 1, el2 = (el << 1) - 1u;
-            const unsigned long long lower = __ballot(ll < lane);
-            if (dl != 0) {
-                if (node - nl1 < span) a.cb += dl;
-                if (end - nl1 < span) a.cB += dl;
-            }
-            const bool same = nl == node;
-            a.T += same ? pl : 0u;
-            lower_same |= __ballot(same) & lower;
-            lower_end |= __ballot(el == end) & lower;
-            a.stopA = min(a.stopA, min(nl - sA, el - sA));
-            a.stopB = min(a.stopB, min(nl2 - e2, el2 - e2));       // (entry nodes at e cut, ends behind e cut)
+            pair_update(a, node, end, nl, el, pl, ll < lane);
         }
-        a.fl = (uint32_t)((lower_same >> lane) & 1ull) | (uint32_t)((lower_end >> lane) & 1ull) << 1;
         return a;
     };
     // ---- every lane: its node, its stretches ----
@@ -567,6 +584,135 @@ __device__ __forceinline__ void wave_walk_body(const DevMAT& m, uint32_t* lds, u
     wave_bytes += wave_sum_u32(bytes);
     if (work_counter && lane == 0 && wave_bytes)
         atomicAdd(work_counter + WALK_COUNTERS + ((blk * W + wv) & (WALK_COUNTERS - 1)), (unsigned long long)wave_bytes);
+}
+
+// -----------------------------------------------------------------------------
+// A read with FEW events: the same pass (wave_read<1, W>) by a GROUP of G lanes, 64 / G reads a wave -- the plain walkers
+// of k_step (walk_kernels.hip), whose walk lane = read is a chain of dependent loads per event and as long as the longest
+// lane of its wave.  Group lane j is list j of the read (k <= WALK8_K <= G lists), then entry j of the concatenated
+// lists (E <= G entries: k_route admits no more to the class).  The groups of a wave are different reads, of different
+// crowns: every number of the read and its stream is a per-lane value, and every exchange is taken by all 64 lanes.
+// (The exchanges are templates on their value's type: a host compiler that parses this header for the sorted pass alone
+// never instantiates them.)
+// -----------------------------------------------------------------------------
+template <typename T> __device__ __forceinline__ T lane_get(T v, uint32_t src) { return __shfl(v, (int)src); }
+// inclusive sum over the lanes of a group up to this one
+template <uint32_t G, typename T> __device__ __forceinline__ T group_scan_add(T v, uint32_t gl) {
+#pragma unroll
+    for (uint32_t d = 1; d < G; d <<= 1) {
+        const T o = __shfl_up(v, d, (int)G);
+        if (gl >= d) v += o;
+    }
+    return v;
+}
+// group-wide minimum / sum, every lane of the group its result (the partners of a butterfly over G stay inside the group)
+template <uint32_t G, typename T> __device__ __forceinline__ T group_min(T v) {
+#pragma unroll
+    for (uint32_t d = 1; d < G; d <<= 1) { const T o = __shfl_xor(v, (int)d); v = o < v ? o : v; }
+    return v;
+}
+template <uint32_t G, typename T> __device__ __forceinline__ T group_sum(T v) {
+#pragma unroll
+    for (uint32_t d = 1; d < G; d <<= 1) v += __shfl_xor(v, (int)d);
+    return v;
+}
+// the lanes of this lane's group among a ballot
+template <uint32_t G> __device__ __forceinline__ uint32_t group_bits(unsigned long long b, uint32_t gbase) { return (uint32_t)(b >> gbase) & ((1u << G) - 1u); }
+
+// read `rd` (have: the group holds one) of the arena slice `wi`, by the G lanes of a group; all 64 lanes call.  The
+// group's first lane writes the four results.
+template <uint32_t G>
+__device__ __forceinline__ void group_read(const DevMAT& m, const DevWalk& ix, uint32_t lane, bool have, uint32_t rd, const WcInfo& wi,
+                                           const uint32_t* __restrict__ read_off, const uint32_t* __restrict__ read_word,
+                                           const int32_t* __restrict__ root_score, uint32_t* __restrict__ best_bfs_j,
+                                           int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                           uint32_t* __restrict__ flags, uint32_t& bytes) {
+    static_assert(G >= WALK8_K && G <= 16 && 64 % G == 0, "a lane per list of the read; the groups tile the wave");
+    const uint32_t gl = lane % G, gbase = lane - gl;
+    // ---- the read's lists: lane j < k holds list j (read_lists, per group) ----
+    uint32_t so = 0, k = 0;
+    // (k <= WALK8_K lists and, below, E <= G entries is k_route's invariant for the list this role reads -- route_kernels.hip,
+    // classify: `events <= walk_max_events` and `k <= WALK8_K` make PLAN_WALK8, and capi.cpp launches this G only for a walk
+    // limit <= G.  The two clamps keep a broken invariant inside the group's lanes and the index's lists: the placement
+    // would then be WRONG without a sign, so whoever changes the classes or the limit must keep both bounds.)
+    if (have) { so = read_off[rd]; k = min(read_off[rd + 1] - so, WALK8_K); }
+    const uint32_t w = gl < k ? read_word[so + gl] : 0u;
+    uint32_t off = 0, len = 0;
+    if (gl < k && w_pos(w) <= m.max_pos) {
+        const uint32_t o0 = ix.ix_head[wi.head_off + w_pos(w)].off, o1 = ix.ix_head[wi.head_off + w_pos(w) + 1].off;
+        off = o0;
+        len = o1 - o0 - 1u;                              // (every list ends in a sentinel)
+    }
+    const uint32_t incl = group_scan_add<G>(len, gl), start = incl - len;
+    const uint32_t E = min(lane_get(incl, gbase + G - 1u), G);                   // (the invariant above: the clamp never binds)
+    const int c0 = (int)__popc(group_bits<G>(__ballot(gl < k && !rw_missing(w) && (rw_mut(w) & rw_ref(w)) == 0), gbase));
+    // ---- entry gl of the concatenated lists (locate): the list that holds it, then that list's offset and read word ----
+    uint32_t jsel = 0, isub = NONE;
+#pragma unroll
+    for (uint32_t j = 0; j < WALK8_K; j++) {
+        const uint32_t sj = lane_get(start, gbase + j), lj = lane_get(len, gbase + j);
+        if (gl - sj < lj) { jsel = j; isub = gl - sj; }
+    }
+    const uint32_t oj = lane_get(off, gbase + jsel), wj = lane_get(w, gbase + jsel);
+    uint32_t node = NONE, end = NONE, pk = 0u, rank = 0u, nst = 0u;
+    int base = 0;
+    if (gl < E && isub != NONE) {
+        const IxEnt ent = ix.ix_ent[oj + isub];
+        node = ent.node;
+        end = ent.end;
+        pk = pack_adjust(ent, wj);
+        base = ent.base;
+        rank = wi.has_pre ? ent.rank & IX_RANK_MASK : ent.rank;
+        nst = ent.nstat;
+    }
+    // ---- what a sequential walk would know at the entry: G exchanges instead of 64 broadcasts ----
+    const PairAcc a = group_pairs<G>(node, end, gl, E, [&](uint32_t ll, uint32_t& nl, uint32_t& el, uint32_t& pl) {
+        nl = lane_get(node, gbase + ll);
+        el = lane_get(end, gbase + ll);
+        pl = lane_get(pk, gbase + ll);
+    });
+    // ---- every lane: its node, its stretches (as wave_read's finish) ----
+    Cand best{(have ? root_score[rd] : 0) + 1, 0xFFFFFFFFu, 0u, 0u};        // the root always competes: nothing worse can win or tie
+    if (node != NONE) {
+        const uint32_t sA = node + 1u;
+        const uint32_t cnt = PK_BIAS * (a.T >> 24);
+        const int dsumT = (int)(a.T & 0xFFu) - (int)cnt, adjT = (int)((a.T >> 8) & 0xFFu) - (int)cnt, dcomT = (int)((a.T >> 16) & 0xFFu) - (int)cnt;
+        if (!(a.fl & 1u)) {
+            const uint32_t nmut = nst & NS_CNT_MASK_DEV, ncom0 = (nst >> 14) & NS_CNT_MASK_DEV;
+            const bool leaf = nst & NS_LEAF_DEV, masked = nst & NS_MASKED_DEV, root = nst & NS_ROOT_DEV;
+            const int c = c0 + a.cb;
+            if (root) { if (base + c + dsumT <= best.bs) cand_take(best, base + c + dsumT, rank, 1u, 0u); }
+            else if (!masked) {
+                const int sc = base + c + adjT, ncom = (int)ncom0 + dcomT;
+                const bool elig = leaf ? (ncom > 0) : (ncom > 0 || ncom == (int)nmut);     // usher_mapper.cpp:455-456
+                if (elig && sc <= best.bs) cand_take(best, sc, rank, 1u, ncom < (int)nmut ? 1u : 0u);
+            }
+            const uint32_t eA = min(sA + a.stopA, wi.n);
+            if (sA < eA) range_candidate(ix, wi, sA, eA, c0 + a.cb + dsumT, best, bytes);
+        }
+        if (!(a.fl & 2u)) {
+            const uint32_t eB = a.stopB >= 0x80000000u ? wi.n : min(end + ((a.stopB + 1u) >> 1), wi.n);     // (no cut behind e: the keys are below 2 n)
+            if (end < eB) range_candidate(ix, wi, end, eB, c0 + a.cB, best, bytes);
+        }
+    }
+    // the stretch from node 0 on is nobody's: the group's first lane asks for it
+    const uint32_t first_node = group_min<G>(node);
+    if (have && gl == 0 && first_node != 0u && wi.n > 0) range_candidate(ix, wi, 0u, min(first_node, wi.n), c0, best, bytes);
+    // ---- the group's best ----
+    const int smin = group_min<G>(best.cnt ? best.bs : 0x7FFFFFFF);
+    const bool at = best.cnt && best.bs == smin;
+    const uint32_t total = group_sum<G>(at ? best.cnt : 0u);
+    const uint32_t rmin = group_min<G>(at ? best.br : 0xFFFFFFFFu);
+    const bool hu = group_bits<G>(__ballot(at && best.br == rmin && best.hu), gbase) != 0u;
+    if (have && gl == 0) {
+        if (best_bfs_j) best_bfs_j[rd] = m.rank2bfs[rmin < m.N ? rmin : 0u];
+        if (score_out) score_out[rd] = smin;
+        if (num_best) num_best[rd] = total;
+        if (flags) flags[rd] = hu ? WEPP_FLAG_HAS_UNIQUE_DEV : 0u;
+        // (as the wave pass counts: list entry, stream record, the read's offsets, words and list heads, root score, rank
+        // -> BFS index and results once; a 32-byte index entry per list entry)
+        bytes += 4 + 64 + 8 + 12 * k + 4 + 4 + 16 + 32 * E;
+    }
 }
 
 }  // namespace

@@ -33,6 +33,7 @@ struct PlaceTunables {
     bool sweep_unfused = false;          // WEPP_SWEEP_UNFUSED=1: one sweep launch per plan, back to back
     bool blind16 = false;                // WEPP_BLIND16=1: the plain walks of 9 - 16 entries launched blind behind k_route too (measured: they start when the walks of 1 - 8 entries end either way)
     bool step_unfused = false;           // WEPP_STEP_UNFUSED=1: plain walks, k_walk_wave and the 8-entry job class as three blind launches behind k_route instead of k_step (the form before it; results identical)
+    bool step_groups = true;             // WEPP_STEP_GROUPS=0: the plain walkers of k_step lane = read (walk_body) instead of by lane groups (place_dev.hpp: group_read; results identical)
     bool scatter_blind = false;          // WEPP_SCATTER_BLIND=1: k_scatter launched blind behind the counters' copy in every call, whether or not a launch reads its lists (the form before the lists became lazy; results identical)
     bool windows_unfused = false;        // WEPP_WINDOWS_UNFUSED=1: one launch per window plan, chunks sized per plan (round 3's form; results identical)
     // seeds: whole-genome samples
@@ -68,6 +69,7 @@ struct PlaceTunables {
         t.sweep_unfused = env::is_set("WEPP_SWEEP_UNFUSED") && env::flag("WEPP_SWEEP_UNFUSED", false);
         t.blind16 = env::flag("WEPP_BLIND16", false);
         t.step_unfused = env::is_set("WEPP_STEP_UNFUSED") && env::flag("WEPP_STEP_UNFUSED", false);
+        t.step_groups = env::flag("WEPP_STEP_GROUPS", true);
         t.scatter_blind = env::is_set("WEPP_SCATTER_BLIND") && env::flag("WEPP_SCATTER_BLIND", false);
         t.windows_unfused = env::is_set("WEPP_WINDOWS_UNFUSED") && env::flag("WEPP_WINDOWS_UNFUSED", false);
         t.seed = env::flag("WEPP_SEED", true);

@@ -525,18 +525,59 @@ __global__ __launch_bounds__(64 * WALK_WAVES) void k_walk(DevMAT m, WalkPlans pl
 }
 
 // -----------------------------------------------------------------------------
+// The plain walkers of k_step by lane groups (place_dev.hpp: group_read): G lanes a read, 64 / G reads a wave.  `wg` = the
+// workgroup's index among the n_wg group-role workgroups of the launch (a multiple of WALK_XCDS).  The grid was sized
+// blind for lane = read, so the list may need up to G times its workgroups: as many as one pass over the list needs --
+// a multiple of WALK_XCDS, at most n_wg -- take reads_per_wg reads per pass and loop; the others leave at once.
+// Within a pass the workgroups of XCD x (wg % 8) hold the x-th CONTIGUOUS eighth of the pass's reads (as `tile` in
+// walk_body): neighbours in the position-sorted list, the same few lists of the index, in one L2.
+// -----------------------------------------------------------------------------
+template <uint32_t G>
+__device__ __forceinline__ void group_body(const DevMAT& m, uint32_t wg, uint32_t n_wg, const uint32_t* __restrict__ read_off,
+                                           const uint32_t* __restrict__ read_word, const int32_t* __restrict__ root_score,
+                                           uint32_t* __restrict__ best_bfs_j, int32_t* __restrict__ score_out, uint32_t* __restrict__ num_best,
+                                           uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
+                                           const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ list, const uint32_t* __restrict__ count) {
+    constexpr uint32_t PER_WAVE = 64 / G, PER_WG = WALK_WAVES * PER_WAVE;
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t n_list = (uint32_t)__builtin_amdgcn_readfirstlane((int)*count);
+    const uint32_t need = ((n_list + PER_WG - 1) / PER_WG + WALK_XCDS - 1) / WALK_XCDS * WALK_XCDS;
+    const uint32_t act = min(need, n_wg);
+    if (wg >= act) return;
+    const uint32_t tile = (wg % WALK_XCDS) * (act / WALK_XCDS) + wg / WALK_XCDS;
+    const DevWalk ix = m.walks[WC_SLOT];                 // the walk arena: every stream is a slice of it
+    uint32_t bytes = 0;
+    // (64 bits: the last pass's slots reach past a list of nearly 2^32 reads)
+    for (unsigned long long base = 0; base < n_list; base += (unsigned long long)act * PER_WG) {
+        const unsigned long long slot = base + tile * PER_WG + wv * PER_WAVE + lane / G;
+        const bool have = slot < n_list;
+        const uint32_t rd = have ? list[slot] : 0u;
+        WcInfo wi{};
+        if (have) wi = m.wc_info[wsid[rd]];
+        group_read<G>(m, ix, lane, have, rd, wi, read_off, read_word, root_score, best_bfs_j, score_out, num_best, flags, bytes);
+    }
+    const uint32_t wave_bytes = wave_sum_u32(bytes);
+    if (work_counter && lane == 0 && wave_bytes)
+        atomicAdd(work_counter + WALK_COUNTERS + ((wg * WALK_WAVES + wv) & (WALK_COUNTERS / 2 - 1)), (unsigned long long)wave_bytes);
+}
+
+// -----------------------------------------------------------------------------
 // k_step: the two common classes of a placement call in ONE launch on the caller's stream, right behind k_route -- the
-// plain walkers of up to WALK8_K entries (k_route's list wlist, lane = read) and the reads with many events (its two-ended
-// list wwlist, lane = list entry: place_dev.hpp wave_walk_body).  A workgroup takes its role from the counters k_route
+// plain walkers of up to WALK8_K entries (k_route's list wlist) and the reads with many events (its two-ended list
+// wwlist, lane = list entry: place_dev.hpp wave_walk_body).  A workgroup takes its role from the counters k_route
 // has left on the device: the first n_wave workgroups -- dispatched first, so the longest items of the step, the reads
-// with more than 64 events, start first -- work on wwlist, every later one is a walker numbered from zero.  n_wave is
+// with more than 64 events, start first -- work on wwlist, every later one on wlist, numbered from zero.  n_wave is
 // what the counters ask for (a workgroup per read with more than 64 events, a wave per smaller one), rounded up to a
-// multiple of WALK_XCDS so that a walker's XCD is still its own index % 8, at most `wave_cap` (beyond, the wave-role
-// workgroups loop); with wave_cap = 0 (the handle cuts such reads into jobs: the lists are empty) this is the blind
-// k_walk<WALK8_K>.  Both roles live in the walkers' dynamic LDS: the launch asks for what k_walk asks.  The LDS leaves
-// the walkers 22 waves a CU; six waves a SIMD is what the registers must leave them (at most 80 VGPRs: the wave role's
+// multiple of WALK_XCDS so that a later workgroup's XCD is still its own index % 8, at most `wave_cap` (beyond, the
+// wave-role workgroups loop); with wave_cap = 0 (no lists of such reads) every workgroup works on wlist.
+// G = 8 / 16: the walkers by lane groups (group_body: the same pass as the wave role's, G lanes a read), for a call whose
+// plain walkers hold at most G events; the kernel then needs the wave role's LDS only, which is static.  G = 0: the
+// walkers lane = read (walk_body), as k_walk<WALK8_K> places them, in the walkers' dynamic LDS (WEPP_STEP_GROUPS=0, and
+// a walk limit above 16 events).  Six waves a SIMD is what the registers must leave (at most 80 VGPRs: the wave role's
 // sorted pass is the widest part, and the compiler is told so that it does not trade a wave for a shorter schedule).
 // -----------------------------------------------------------------------------
+template <uint32_t G>
 __global__ __launch_bounds__(64 * WALK_WAVES) __attribute__((amdgpu_waves_per_eu(6))) void k_step(DevMAT m, uint32_t sd_rows, uint32_t wave_cap, uint32_t n_reads,
                                               const uint32_t* __restrict__ read_off,
                                               const uint32_t* __restrict__ read_word,
@@ -546,7 +587,14 @@ __global__ __launch_bounds__(64 * WALK_WAVES) __attribute__((amdgpu_waves_per_eu
                                               const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ wlist,
                                               const uint32_t* __restrict__ wcount, const uint32_t* __restrict__ wwlist,
                                               const uint32_t* __restrict__ wwcount) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds_all[];
+    uint32_t* lds_all;
+    if constexpr (G != 0) {
+        __shared__ __attribute__((aligned(16))) uint32_t lds_wave[ww_lds_words(WALK_WAVES)];
+        lds_all = lds_wave;
+    } else {
+        extern __shared__ __attribute__((aligned(16))) uint32_t lds_dyn[];
+        lds_all = lds_dyn;
+    }
     uint32_t n_wave = 0, n_small = 0, n_big = 0;
     if (wave_cap) {
         n_small = (uint32_t)__builtin_amdgcn_readfirstlane((int)wwcount[0]);
@@ -558,6 +606,9 @@ __global__ __launch_bounds__(64 * WALK_WAVES) __attribute__((amdgpu_waves_per_eu
     if (blockIdx.x < n_wave) {
         wave_walk_body<WALK_WAVES>(m, lds_all, blockIdx.x, n_wave, wwlist, n_small, n_big, n_reads, read_off, read_word, root_score, best_bfs_j, score_out,
                                    num_best, flags, work_counter, wsid);
+    } else if constexpr (G != 0) {
+        group_body<G>(m, blockIdx.x - n_wave, gridDim.x - n_wave, read_off, read_word, root_score, best_bfs_j, score_out, num_best, flags, work_counter, wsid,
+                      wlist, wcount);
     } else {
         WalkPlans pl{};
         pl.n = 1;
@@ -694,18 +745,26 @@ hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows,
     return hipGetLastError();
 }
 
-hipError_t launch_step(const DevMAT& m, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
+hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
                        const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
                        int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
-    static_assert(STEP_WAVE_WGS % WALK_XCDS == 0, "the walkers behind the wave-role workgroups keep their XCD order");
+    static_assert(STEP_WAVE_WGS % WALK_XCDS == 0 && WALK_PLAN_ALIGN % (WALK_XCDS * WALK_WAVES) == 0,
+                  "the workgroups behind the wave-role ones keep their XCD order, and their number is a multiple of the XCDs");
     if (max_reads == 0) return hipSuccess;
+    if (group != 0 && group != 8 && group != 16) return hipErrorInvalidValue;
     const uint32_t wave_cap = wwlist ? STEP_WAVE_WGS : 0u;
     const uint32_t sd = walk_stack_rows(stack_rows, WALK8_STACK);
-    // (with the default stack rows the walkers' request is the larger one)
-    const uint32_t lds = std::max(walk_lds_bytes(WALK8_K, sd), wave_cap ? ww_lds_words(WALK_WAVES) * 4u : 0u);
+    // (the grid is the one of lane = read whatever the form: with groups its workgroups loop when the list needs more)
     const dim3 grid(wave_cap + walk_plan_waves(max_reads) / WALK_WAVES), block(64 * WALK_WAVES);
-    hipLaunchKernelGGL(k_step, grid, block, lds, stream, m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags,
-                       work_counter, wsid, wlist, wcount, wwlist, wwcount);
+#define WEPP_STEP_ARGS m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, wlist, wcount, wwlist, wwcount
+    if (group == 8) hipLaunchKernelGGL(k_step<8>, grid, block, 0, stream, WEPP_STEP_ARGS);
+    else if (group == 16) hipLaunchKernelGGL(k_step<16>, grid, block, 0, stream, WEPP_STEP_ARGS);
+    else {
+        // (with the default stack rows the walkers' request is the larger one)
+        const uint32_t lds = std::max(walk_lds_bytes(WALK8_K, sd), wave_cap ? ww_lds_words(WALK_WAVES) * 4u : 0u);
+        hipLaunchKernelGGL(k_step<0>, grid, block, lds, stream, WEPP_STEP_ARGS);
+    }
+#undef WEPP_STEP_ARGS
     return hipGetLastError();
 }
 
