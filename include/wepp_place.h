@@ -186,6 +186,41 @@ int wepp_best_nodes(wepp_mat_t *mat, const uint32_t *read_off, const uint32_t *r
                     const int32_t *score, const uint32_t *num_best, uint64_t *best_off, uint32_t *best_nodes,
                     uint64_t capacity);
 
+/* ---- clade assignment of placed samples ------------------------------------------------ *
+ * Replaces the loop of src/usher_common.cpp:597-616 (one Tree::get_clade_assignment, src/mutation_annotated_tree.cpp:
+ * 923-931, per annotation column and optimal node of a sample, then a sort of the names) for a whole batch.
+ * Names never cross this boundary.  For every annotation column c the caller numbers the DISTINCT names of the column,
+ * "UNDEFINED" among them, 1, 2, 3 .. BY THEIR RANK UNDER std::string::operator< (byte-wise, a prefix before the longer
+ * name): ascending id is then the order in which std::sort leaves Missing_Sample::clade_assignments[c] (:614), and the
+ * histograms below come out in the order the -D writer prints them (:937-954).  Any other numbering still counts
+ * correctly but lists the clades in another order than the reference.
+ *   clade_id[c * n_nodes + caller node id]   0 for a node without annotation in column c, its name's id otherwise
+ *   undefined_id[c]                          the id of "UNDEFINED" in column c (what a node without annotated ancestor gets)
+ * The call builds and uploads, per column and node, the nearest annotated ancestor including the node and the nearest
+ * one excluding it (one top-down pass; once per call, not per sample).  n_columns > 8: WEPP_ELIMIT.  n_columns == 0
+ * clears the tables.  Calling again replaces them. */
+int wepp_mat_set_clades(wepp_mat_t *mat, uint32_t n_columns, const uint32_t *clade_id, const uint32_t *undefined_id);
+/* best_bfs_j = what wepp_place_batch returned for these reads, best_off / best_nodes = what wepp_best_nodes returned.
+ * For pair (r, k) with node n = bfs[best_nodes[best_off[r] + k]]: include_self = !n->is_leaf() && !has_unique(r, n)
+ * (:607; has_unique as mapper2_body computes it, src/usher_mapper.cpp:184-262), and the pair's clade in column c is the
+ * nearest annotated ancestor of n including / excluding n accordingly.
+ *   best_clade[c * n_reads + r]   the clade of the pair whose node is best_bfs_j[r]: best_clade_assignment[c] (:610-612)
+ *   hist_off[n_columns * n_reads + 1]   CSR over (column, read), segment c * n_reads + r
+ *   hist_clade / hist_count       the distinct clades of the read's pairs in ascending id with their counts; the counts
+ *                                 of a segment sum to num_best[r]
+ * capacity = size of hist_clade / hist_count; WEPP_ELIMIT (best_clade complete, hist_off filled: hist_off[n_columns *
+ * n_reads] is the needed size) when it is too small.  WEPP_EINVAL: no clades set on the handle, a best_nodes entry that
+ * is no BFS index, best_bfs_j[r] not among read r's nodes.  WEPP_ELIMIT besides: n_columns * (pairs of all reads) or
+ * n_columns * (n_reads + 1) >= 2^32; split the batch.  Any output pointer may be NULL (without hist_clade and hist_count
+ * the capacity is not looked at; without all three nothing is counted).  Integer work: bit-identical run to run. */
+int wepp_clade_assign(wepp_mat_t *mat, const uint32_t *read_off, const uint32_t *read_word, uint32_t n_reads,
+                      const uint32_t *best_bfs_j, const uint64_t *best_off, const uint32_t *best_nodes,
+                      uint32_t *best_clade, uint64_t *hist_off, uint32_t *hist_clade, uint32_t *hist_count,
+                      uint64_t capacity);
+/* device time of the calling thread's last wepp_clade_assign by phase (HIP events, ms): the pair kernel; the sorts of
+ * the segments, run heads and their scan; run starts, counts and the copies out */
+int wepp_clade_last_timing(double *pairs_ms, double *count_ms, double *finish_ms);
+
 /* ---- excess mutations of (sample, node) pairs --------------------------------------- *
  * node_excess_mutations[j] as mapper2_body appends it with compute_vecs for sample
  * pair_read[i] at the node with BFS index pair_bfs_j[i]: first the node's own mutations the

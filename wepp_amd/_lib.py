@@ -182,6 +182,9 @@ _SIGS = {
     "wepp_place_batch": (ctypes.c_int, [_V, _V, _V, ctypes.c_uint32, _V, _V, _V, _V, _V]),
     "wepp_imputed_mutations": (ctypes.c_int, [_V, _V, _V, ctypes.c_uint32, _V, _V, _V, _V, ctypes.c_uint64]),
     "wepp_best_nodes": (ctypes.c_int, [_V, _V, _V, ctypes.c_uint32, _V, _V, _V, _V, ctypes.c_uint64]),
+    "wepp_mat_set_clades": (ctypes.c_int, [_V, ctypes.c_uint32, _V, _V]),
+    "wepp_clade_assign": (ctypes.c_int, [_V, _V, _V, ctypes.c_uint32, _V, _V, _V, _V, _V, _V, _V, ctypes.c_uint64]),
+    "wepp_clade_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
     "wepp_excess_mutations": (ctypes.c_int, [_V, _V, _V, ctypes.c_uint32, ctypes.c_uint32, _V, _V, _V, _V, _V, _V, _V,
                                              ctypes.c_uint64]),
     "wepp_place_batch_device": (

@@ -393,6 +393,7 @@ class Mat:
         check(lib.wepp_mat_get_stats(self._h, ctypes.byref(st)))
         self.stats = st
         self.n_nodes = int(st.n_nodes)
+        self.clade_columns = 0   # annotation columns given to set_clades
 
     def bfs_order(self):
         out = np.zeros(self.n_nodes, dtype=np.uint32)
@@ -451,6 +452,11 @@ class Mat:
     def best_nodes(self, reads, res):
         """wepp_best_nodes: best_j_vec of every read (BFS indices of all optimal nodes, ascending) as a list of
         arrays; res = the PlacementResult of place_batch for the same reads."""
+        off, nodes = self.best_nodes_csr(reads, res)
+        return [nodes[int(off[r]):int(off[r + 1])] for r in range(reads.n_reads)]
+
+    def best_nodes_csr(self, reads, res):
+        """The same as the CSR the C-ABI delivers: (best_off[n_reads + 1] uint64, best_nodes uint32)."""
         n = reads.n_reads
         off = np.zeros(n + 1, np.uint64)
         cap = int(res.num_best.astype(np.uint64).sum())
@@ -458,7 +464,44 @@ class Mat:
         rw = reads.read_word if reads.read_word.size else np.zeros(1, np.uint32)
         check(lib.wepp_best_nodes(self._h, _ptr(reads.read_off), _ptr(rw), n, _ptr(np.ascontiguousarray(res.score, np.int32)),
                                   _ptr(np.ascontiguousarray(res.num_best, np.uint32)), _ptr(off), _ptr(nodes), cap))
-        return [nodes[int(off[r]):int(off[r + 1])] for r in range(n)]
+        return off, nodes[:cap]
+
+    def set_clades(self, clade_id, undefined_id):
+        """wepp_mat_set_clades: clade_id[c, caller node id] (0 = not annotated) and undefined_id[c], numbered by the
+        names' rank (number_clade_names); zero columns clears the tables."""
+        cid = np.ascontiguousarray(clade_id, np.uint32).reshape(-1, self.n_nodes) if np.size(clade_id) else np.zeros((0, self.n_nodes), np.uint32)
+        und = np.ascontiguousarray(undefined_id, np.uint32).reshape(-1)
+        if und.shape[0] != cid.shape[0]:
+            raise ValueError("undefined_id holds one id per column")
+        check(lib.wepp_mat_set_clades(self._h, cid.shape[0], _ptr(cid) if cid.size else None, _ptr(und) if und.size else None))
+        self.clade_columns = cid.shape[0]
+
+    def clade_assign(self, reads, res, best_off, best_nodes, capacity=None, want_hist=True):
+        """wepp_clade_assign for the reads of place_batch (res) and their best_nodes_csr: (best_clade [C, n_reads],
+        hist_off [C * n_reads + 1], hist_clade, hist_count).  capacity=None sizes the histograms with a second call."""
+        n, C = reads.n_reads, self.clade_columns
+        bc = np.zeros((C, n), np.uint32)
+        rw = reads.read_word if reads.read_word.size else np.zeros(1, np.uint32)
+        bj = np.ascontiguousarray(res.best_bfs_j, np.uint32)
+        boff = np.ascontiguousarray(best_off, np.uint64)
+        bn = np.ascontiguousarray(best_nodes, np.uint32)
+        bnp = bn if bn.size else np.zeros(1, np.uint32)
+        if not want_hist:
+            check(lib.wepp_clade_assign(self._h, _ptr(reads.read_off), _ptr(rw), n, _ptr(bj), _ptr(boff), _ptr(bnp), _ptr(bc),
+                                        None, None, None, 0))
+            return bc, None, None, None
+        hoff = np.zeros(C * n + 1, np.uint64)
+        cap = 0 if capacity is None else int(capacity)
+        while True:
+            hc = np.zeros(max(cap, 1), np.uint32); hn = np.zeros(max(cap, 1), np.uint32)
+            rc = lib.wepp_clade_assign(self._h, _ptr(reads.read_off), _ptr(rw), n, _ptr(bj), _ptr(boff), _ptr(bnp), _ptr(bc),
+                                       _ptr(hoff), _ptr(hc), _ptr(hn), cap)
+            if rc == 4 and capacity is None and int(hoff[-1]) > cap:
+                cap = int(hoff[-1])
+                continue
+            check(rc)
+            break
+        return bc, hoff, hc[:int(hoff[-1])], hn[:int(hoff[-1])]
 
     def excess_mutations(self, reads, pair_read, pair_bfs_j):
         """wepp_excess_mutations: per (read, node) pair the list of (position, ref, par, mut)."""
@@ -786,6 +829,31 @@ def epp_last_timing():
                                    ctypes.byref(j)))
     return dict(select_ms=d[0].value, sweep1_ms=d[1].value, sweep2_ms=d[2].value, finish_ms=d[3].value,
                 events_swept=ev.value, stream_events=se.value, groups=g.value, jobs=j.value)
+
+
+def number_clade_names(columns):
+    """columns[c][node id] = the node's annotation in column c ('' = none).  Returns (clade_id [C, N] uint32,
+    undefined_id [C] uint32, names) with names[c][id - 1] the name numbered id: the distinct names of the column and
+    'UNDEFINED', by their rank under byte-wise comparison (std::string::operator<), as wepp_mat_set_clades asks."""
+    C = len(columns)
+    N = len(columns[0]) if C else 0
+    cid = np.zeros((C, N), np.uint32)
+    und = np.zeros(C, np.uint32)
+    names = []
+    for c, col in enumerate(columns):
+        order = sorted(set(a for a in col if a != "") | {"UNDEFINED"}, key=lambda a: a.encode("utf-8"))
+        rank = {a: i + 1 for i, a in enumerate(order)}
+        cid[c] = [rank[a] if a != "" else 0 for a in col]
+        und[c] = rank["UNDEFINED"]
+        names.append(order)
+    return cid, und, names
+
+
+def clade_last_timing():
+    """Device time by phase (ms) of this thread's last Mat.clade_assign call."""
+    d = [ctypes.c_double() for _ in range(3)]
+    check(lib.wepp_clade_last_timing(*[ctypes.byref(x) for x in d]))
+    return dict(pairs_ms=d[0].value, count_ms=d[1].value, finish_ms=d[2].value)
 
 
 def epp_assign_last_timing():

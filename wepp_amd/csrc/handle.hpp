@@ -91,6 +91,13 @@ struct wepp_mat {
     // (-1: not read yet, 0: sized by the memory budget)
     const uint32_t* nbr_dfs_end = nullptr;
     int nbr_pass_cols = -1;
+    // wepp_mat_set_clades (clades_capi.cpp): [columns][2][N] nearest annotated ancestor of every DFS node, excluding /
+    // including the node; replaced by every call, freed with the handle (in `allocs` it would pile up)
+    uint32_t clade_columns = 0;
+    struct DevTable {
+        uint32_t* ptr = nullptr;
+        ~DevTable() { if (ptr) (void)hipFree(ptr); }
+    } clade_tab;
     std::vector<uint32_t> epp_pending;   // EPP lists of the last wepp_epp_map that did not fit the caller's buffer (wepp_epp_fetch_lists)
     std::vector<void*> allocs;
     uint32_t tile_reads = 64;

@@ -130,8 +130,26 @@ __device__ __forceinline__ uint32_t find_entry(SPtr S, uint32_t off, uint32_t k,
     return NONE;
 }
 
+// has_unique of the node with DFS index d for the read with entries read_word[so .. so + k), from the node's own
+// mutation words (usher_mapper.cpp:184,199,262): the emitted flag of a read's winner, and the flag of every optimal
+// node of a read in clades_kernels.hip
+__device__ __forceinline__ uint32_t node_has_unique(const DevMAT& m, uint32_t d, const uint32_t* __restrict__ read_word,
+                                                    uint32_t so, uint32_t k) {
+    const uint32_t st = m.nstat[d];
+    if (st & NS_ROOT_DEV) return 0u;
+    if (st & NS_MASKED_DEV) return 1u;
+    int ncom = (int)((st >> 14) & NS_CNT_MASK_DEV);
+    int dummy = 0;
+    for (uint32_t w = m.node_woff[d]; w < m.node_woff[d + 1]; w++) {
+        const uint32_t tw = m.words[w];
+        const uint32_t s = find_entry(read_word, so, k, w_pos(tw));
+        if (s != NONE) own_adjust(tw, s, dummy, ncom);
+    }
+    return (ncom < (int)(st & NS_CNT_MASK_DEV)) ? 1u : 0u;
+}
+
 // the per-read outputs from a read's best (score, rank, count): the reference's BFS index of the winner and
-// its has_unique flag recomputed from its own mutations (usher_mapper.cpp:184,199,262,472,492)
+// its has_unique flag recomputed from its own mutations (usher_mapper.cpp:472,492)
 __device__ __forceinline__ void emit_result(const DevMAT& m, uint32_t r, const uint32_t* __restrict__ read_off,
                                             const uint32_t* __restrict__ read_word, int bs, uint32_t br, uint32_t cnt,
                                             uint32_t* __restrict__ best_bfs_j, int32_t* __restrict__ score,
@@ -139,22 +157,8 @@ __device__ __forceinline__ void emit_result(const DevMAT& m, uint32_t r, const u
     // the root always competes, so some chunk reports it or better; the clamp only keeps a broken
     // invariant from becoming an out-of-bounds read
     const uint32_t d = m.rank2dfs[br < m.N ? br : 0u];
-    const uint32_t st = m.nstat[d];
-    uint32_t hu = 0;
-    if (!(st & NS_ROOT_DEV)) {
-        if (st & NS_MASKED_DEV) hu = 1;
-        else {
-            int ncom = (int)((st >> 14) & NS_CNT_MASK_DEV);
-            int dummy = 0;
-            const uint32_t so = read_off[r], k = read_off[r + 1] - so;
-            for (uint32_t w = m.node_woff[d]; w < m.node_woff[d + 1]; w++) {
-                const uint32_t tw = m.words[w];
-                const uint32_t s = find_entry(read_word, so, k, w_pos(tw));
-                if (s != NONE) own_adjust(tw, s, dummy, ncom);
-            }
-            hu = (ncom < (int)(st & NS_CNT_MASK_DEV)) ? 1u : 0u;
-        }
-    }
+    const uint32_t so = read_off[r];
+    const uint32_t hu = node_has_unique(m, d, read_word, so, read_off[r + 1] - so);
     if (best_bfs_j) best_bfs_j[r] = m.dfs2bfs[d];
     if (score) score[r] = bs;
     if (num_best) num_best[r] = cnt;

@@ -101,6 +101,7 @@ Node* Tree::create_node(std::string const& identifier, Node* par, float branch_l
     n->branch_length = branch_length;
     n->parent = par;
     n->level = par->level + 1;
+    n->clade_annotations.assign(get_num_annotations(), std::string());   // :871-874
     slot.first->second = n;
     par->children.push_back(n);
     return n;
@@ -115,6 +116,14 @@ Node* Tree::create_node(std::string const& identifier, std::string const& parent
 Node* Tree::get_node(std::string const& identifier) const {
     auto it = all_nodes.find(identifier);
     return it == all_nodes.end() ? nullptr : it->second;
+}
+
+std::string Tree::get_clade_assignment(const Node* n, int clade_id, bool include_self) const {
+    if (clade_id < 0 || (size_t)clade_id >= get_num_annotations()) throw mat_error("get_clade_assignment: no annotation column " + std::to_string(clade_id));
+    for (const Node* anc = include_self ? n : (n ? n->parent : nullptr); anc; anc = anc->parent)
+        if (anc->clade_annotations.size() > (size_t)clade_id && !anc->clade_annotations[(size_t)clade_id].empty())
+            return anc->clade_annotations[(size_t)clade_id];
+    return "UNDEFINED";
 }
 
 size_t Tree::get_num_leaves(Node* node) const {
@@ -333,7 +342,7 @@ Tree load_mutation_annotated_tree(std::string const& filename) {
     lap("read + inflate");
     Wire top{(const uint8_t*)raw.data(), (const uint8_t*)raw.data() + raw.size()};
     std::string newick;
-    std::vector<Wire> node_lists;
+    std::vector<Wire> node_lists, metadata;
     std::vector<std::pair<std::string, std::vector<std::string>>> condensed;
     while (!top.eof()) {
         uint64_t key = top.varint();
@@ -350,7 +359,8 @@ Tree load_mutation_annotated_tree(std::string const& filename) {
                 else c.skip((uint32_t)(k2 & 7));
             }
             condensed.push_back(std::move(cn));
-        } else top.skip(wt);
+        } else if (field == 4 && wt == 2) metadata.push_back(top.sub());
+        else top.skip(wt);
     }
     lap("message scan");
     Tree tree = create_tree_from_newick_string(newick);
@@ -359,8 +369,20 @@ Tree load_mutation_annotated_tree(std::string const& filename) {
     if (node_lists.size() < dfs.size())
         throw mat_error("ERROR: .pb holds " + std::to_string(node_lists.size()) + " mutation lists for " +
                         std::to_string(dfs.size()) + " nodes");
+    // node_metadata, one per node in DFS order like the mutation lists (:549, :561-565); a .pb without any has no columns
+    if (!metadata.empty() && metadata.size() < dfs.size())
+        throw mat_error("ERROR: .pb holds " + std::to_string(metadata.size()) + " metadata entries for " +
+                        std::to_string(dfs.size()) + " nodes");
     for (size_t idx = 0; idx < dfs.size(); idx++) {
         Node* node = dfs[idx];
+        if (!metadata.empty()) {
+            Wire md = metadata[idx];
+            while (!md.eof()) {
+                uint64_t key = md.varint();
+                if ((key >> 3) == 1 && (key & 7) == 2) node->clade_annotations.push_back(md.str());
+                else md.skip((uint32_t)(key & 7));
+            }
+        }
         Wire lst = node_lists[idx];
         while (!lst.eof()) {
             uint64_t key = lst.varint();
@@ -398,6 +420,13 @@ Tree load_mutation_annotated_tree(std::string const& filename) {
 void save_mutation_annotated_tree(const Tree& tree, std::string const& filename) {
     std::string out;
     put_len(out, 1, get_newick_string(tree));
+    // node_metadata (:621-625) only for a tree that has annotation columns: a tree without stays the bytes it was
+    if (tree.get_num_annotations() > 0)
+        for (Node* n : tree.depth_first_expansion()) {
+            std::string md;
+            for (auto& a : n->clade_annotations) put_len(md, 1, a);
+            put_len(out, 4, md);
+        }
     for (Node* n : tree.depth_first_expansion()) {
         std::string lst;
         for (auto& m : n->mutations) {

@@ -46,6 +46,7 @@ class Node {   // mutation_annotated_tree.hpp:80-102
     Node* parent = nullptr;
     std::vector<Node*> children;
     std::vector<Mutation> mutations;
+    std::vector<std::string> clade_annotations;   // one per annotation column, "" = none (node_metadata.clade_annotations)
     size_t dfs_idx = 0, dfs_end_idx = 0;
     bool is_leaf() const { return children.empty(); }
     bool is_root() const { return parent == nullptr; }
@@ -75,6 +76,11 @@ class Tree {   // mutation_annotated_tree.hpp:104-152
     std::vector<Node*> breadth_first_expansion(std::string nid = "") const;
     std::vector<Node*> depth_first_expansion(Node* node = nullptr) const;   // also sets dfs_idx / dfs_end_idx
     size_t size() const { return all_nodes.size(); }
+    // annotation columns = those of the root (:767-773); new nodes get that many empty ones (:871-874, :1240-1260)
+    size_t get_num_annotations() const { return root ? root->clade_annotations.size() : 0; }
+    // the first non-empty annotation in column clade_id on the way from n (include_self) or its parent to the root,
+    // "UNDEFINED" when there is none (:923-931)
+    std::string get_clade_assignment(const Node* n, int clade_id, bool include_self) const;
     void reserve(size_t n_nodes);          // room in the name table for n_nodes nodes (no rehash while they are created)
     // condensed identical-sequence leaves back into separate leaves (mutation_annotated_tree.cpp:1224-1272)
     void uncondense_leaves();

@@ -13,6 +13,7 @@
 #include <unordered_map>
 
 #include "../../include/wepp_place.h"
+#include "clade_names.hpp"
 
 namespace {
 struct FileCloser {
@@ -85,16 +86,24 @@ struct ScoreChunk {
     std::string error;
 };
 
+// the clade assignments of a device's placed samples (usher_common.cpp:597-616)
+struct ShardClades {
+    std::vector<uint32_t> sel;               // the samples (indices into the placement arrays) that passed :580
+    std::vector<uint32_t> best;              // [column * sel.size() + i]: best_clade_assignment
+    std::vector<uint64_t> hist_off;          // -D: the sorted clade_assignments as runs, CSR over (column, i)
+    std::vector<uint32_t> hist_clade, hist_count;
+};
+
 }  // namespace
 
 int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t max_parsimony,
                         bool print_parsimony_scores, std::vector<Missing_Sample>& missing_samples,
                         std::vector<std::string>& low_confidence_samples, MAT::Tree* T,
                         std::vector<usher_place_result>* results, int device, bool sort_before_placement_1,
-                        bool sort_before_placement_2, bool sort_before_placement_3, bool reverse_sort) {
+                        bool sort_before_placement_2, bool sort_before_placement_3, bool reverse_sort, bool detailed_clades) {
     return usher_place_samples(outdir, max_uncertainty, max_parsimony, print_parsimony_scores, missing_samples,
                                low_confidence_samples, T, std::vector<int>{device}, results, sort_before_placement_1,
-                               sort_before_placement_2, sort_before_placement_3, reverse_sort);
+                               sort_before_placement_2, sort_before_placement_3, reverse_sort, detailed_clades);
 }
 
 int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t max_parsimony,
@@ -102,7 +111,7 @@ int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t m
                         std::vector<std::string>& low_confidence_samples, MAT::Tree* T,
                         const std::vector<int>& devices, std::vector<usher_place_result>* results,
                         bool sort_before_placement_1, bool sort_before_placement_2, bool sort_before_placement_3,
-                        bool reverse_sort) {
+                        bool reverse_sort, bool detailed_clades) {
     if (!T || !T->root) {
         fprintf(stderr, "ERROR: empty tree!\n");
         return 1;
@@ -157,6 +166,25 @@ int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t m
     std::vector<std::vector<int32_t>> shard_imp_pos(G);
     std::vector<std::vector<uint8_t>> shard_imp_nuc(G);
     auto shard_lo = [&](uint32_t g) { return (uint32_t)((uint64_t)R * g / G); };
+    // clades.txt is written for a tree with annotation columns (usher_common.cpp:906-911); the samples get their
+    // clades in the placement branch only (:580, :597-616), which the -p mode never enters
+    // Departure: the reference also writes the file (every clade "UNDEFINED") for a tree whose columns are all empty;
+    // here such a tree counts as one without annotations, so that what was written for it before stays as it was.
+    const size_t num_annotations = T->get_num_annotations();
+    bool any_annotation = false;
+    for (size_t k = 0; k < total_nodes && !any_annotation; k++)
+        for (auto& a : bfs[k]->clade_annotations) any_annotation = any_annotation || !a.empty();
+    const bool write_clades = num_annotations > 0 && any_annotation && !outdir.empty() && !missing_samples.empty();
+    const bool assign_clades = write_clades && !print_parsimony_scores;
+    CladeNumbering clade_names;
+    if (assign_clades) {
+        if (num_annotations > 8) {
+            fprintf(stderr, "ERROR: %zu annotation columns, at most 8 are supported\n", num_annotations);
+            return 1;
+        }
+        clade_names = number_clades(bfs, num_annotations);
+    }
+    std::vector<ShardClades> shard_clades(G);
     // ONE flatten for the node (the reference pays its expansion once per sample, usher_common.cpp:339); every device
     // thread uploads the same image
     wepp_flat_t* image = nullptr;
@@ -196,6 +224,45 @@ int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t m
         for (uint32_t i = 0; i < n; i++) shard_imp_cnt[g][i] = ioff[i + 1] - ioff[i];
         shard_imp_pos[g].resize(ioff[n]);
         shard_imp_nuc[g].resize(ioff[n]);
+        if (!assign_clades) return;
+        // the clades of this device's samples that pass :580: all their optimal nodes, then one call
+        ShardClades& sc = shard_clades[g];
+        const uint32_t C = (uint32_t)num_annotations;
+        for (uint32_t q = lo; q < hi; q++)
+            if (num_best[q] <= max_uncertainty && best_sd[q] <= (int)max_parsimony) sc.sel.push_back(q);
+        const uint32_t m = (uint32_t)sc.sel.size();
+        if (m == 0) return;
+        if (wepp_mat_set_clades(mats[g], C, clade_names.clade_id.data(), clade_names.undefined_id.data()) != WEPP_OK) {
+            errors[g] = wepp_last_error();
+            return;
+        }
+        gather_reads(read_off, read_word, sc.sel.data(), 0, m, off, words);
+        std::vector<uint32_t> s_bj(m), s_nb(m);
+        std::vector<int32_t> s_sd(m);
+        uint64_t n_pairs = 0, cap = 0;
+        for (uint32_t i = 0; i < m; i++) {
+            s_bj[i] = best_j[sc.sel[i]]; s_nb[i] = num_best[sc.sel[i]]; s_sd[i] = best_sd[sc.sel[i]];
+            n_pairs += s_nb[i];
+            // (a segment holds at most as many runs as it has pairs, and as its column has names)
+            for (uint32_t c = 0; c < C; c++) cap += std::min<uint64_t>(s_nb[i], clade_names.names[c].size());
+        }
+        std::vector<uint64_t> best_off(m + 1);
+        std::vector<uint32_t> best_nodes(n_pairs + 1);
+        if (wepp_best_nodes(mats[g], off.data(), words.data(), m, s_sd.data(), s_nb.data(), best_off.data(), best_nodes.data(),
+                            n_pairs) != WEPP_OK) {
+            errors[g] = wepp_last_error();
+            return;
+        }
+        sc.best.resize((size_t)C * m);
+        if (detailed_clades) {
+            sc.hist_off.resize((size_t)C * m + 1);
+            sc.hist_clade.resize(cap + 1);
+            sc.hist_count.resize(cap + 1);
+        }
+        if (wepp_clade_assign(mats[g], off.data(), words.data(), m, s_bj.data(), best_off.data(), best_nodes.data(), sc.best.data(),
+                              detailed_clades ? sc.hist_off.data() : nullptr, detailed_clades ? sc.hist_clade.data() : nullptr,
+                              detailed_clades ? sc.hist_count.data() : nullptr, cap) != WEPP_OK)
+            errors[g] = wepp_last_error();
     };
     auto run_on_devices = [&](const std::function<void(uint32_t)>& fn) {
         if (G == 1) { fn(0); return; }
@@ -390,6 +457,38 @@ int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t m
         if (results)
             results->push_back({best_set_difference, nb, (size_t)best_j[q], bfs[best_j[q]],
                                 (flags[q] & WEPP_FLAG_HAS_UNIQUE) != 0});
+    }
+    if (write_clades) {
+        // usher_common.cpp:914-961: one row per placed sample in the order of missing_samples, the best node's clade
+        // per column and, with -D, every clade of the optimal placements with its share
+        const std::string fn = outdir + "/clades.txt";
+        fprintf(stderr, "Writing clade annotations to file %s \n", fn.c_str());                                  // :919
+        FileCloser clades;
+        clades.f = fopen(fn.c_str(), "w");
+        if (!clades.f) {
+            fprintf(stderr, "ERROR: cannot write to %s\n", outdir.c_str());
+            destroy_all();
+            return 1;
+        }
+        for (uint32_t g = 0; g < G; g++) {
+            const ShardClades& sc = shard_clades[g];
+            const size_t m = sc.sel.size();
+            for (size_t i = 0; i < m; i++) {
+                fprintf(clades.f, "%s\t", missing_samples[todo[sc.sel[i]]].name.c_str());                       // :931
+                for (size_t k = 0; k < num_annotations; k++) {
+                    fprintf(clades.f, "%s", clade_names.name(k, sc.best[k * m + i]).c_str());
+                    if (detailed_clades) {                                                                      // :935-955
+                        fprintf(clades.f, "*|");
+                        const uint64_t lo = sc.hist_off[k * m + i], hi = sc.hist_off[k * m + i + 1];
+                        for (uint64_t x = lo; x < hi; x++)
+                            fprintf(clades.f, "%s(%i/%zu)%s", clade_names.name(k, sc.hist_clade[x]).c_str(), (int)sc.hist_count[x],
+                                    (size_t)num_best[sc.sel[i]], x + 1 < hi ? "," : "");
+                    }
+                    if (k + 1 < num_annotations) fprintf(clades.f, "\t");
+                }
+                fprintf(clades.f, "\n");
+            }
+        }
     }
     destroy_all();
     usher_last_timing.write_s = now_s() - t_mark;

@@ -41,12 +41,18 @@ extern usher_place_timing usher_last_timing;
 //                            (3: by number of ambiguous bases, reorders missing_samples) and
 //                            :184-298 (1: by score then number of optimal placements, 2: the
 //                            other way round); with --no-add they only change the row order
+//   detailed_clades          -D: clades.txt lists, per column, every clade of the parsimony-optimal placements
+//                            with its share behind the best node's clade (:935-955)
+// A tree with annotation columns gets clades.txt in `outdir` (:906-967): one row per sample placed within the
+// thresholds (:580), in the order of missing_samples; the clades come from wepp_best_nodes + wepp_clade_assign.
+// Departure: a tree whose annotation columns are all empty gets no file (the reference writes "UNDEFINED" rows), so
+// that the output for such trees is what it was before the clades existed.
 int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t max_parsimony,
                         bool print_parsimony_scores, std::vector<Missing_Sample>& missing_samples,
                         std::vector<std::string>& low_confidence_samples, MAT::Tree* T,
                         std::vector<usher_place_result>* results = nullptr, int device = 0,
                         bool sort_before_placement_1 = false, bool sort_before_placement_2 = false,
-                        bool sort_before_placement_3 = false, bool reverse_sort = false);
+                        bool sort_before_placement_3 = false, bool reverse_sort = false, bool detailed_clades = false);
 // The same over several GPUs of one node: one host thread and one handle per entry of `devices`
 // (HIP device indices; an index may repeat), device g placing the contiguous range of samples
 // [R*g/G, R*(g+1)/G) -- the per-sample work of usher_common.cpp:386-446 is independent between
@@ -56,4 +62,4 @@ int usher_place_samples(std::string outdir, uint32_t max_uncertainty, uint32_t m
                         std::vector<std::string>& low_confidence_samples, MAT::Tree* T,
                         const std::vector<int>& devices, std::vector<usher_place_result>* results = nullptr,
                         bool sort_before_placement_1 = false, bool sort_before_placement_2 = false,
-                        bool sort_before_placement_3 = false, bool reverse_sort = false);
+                        bool sort_before_placement_3 = false, bool reverse_sort = false, bool detailed_clades = false);

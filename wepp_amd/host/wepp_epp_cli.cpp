@@ -3,6 +3,7 @@
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
 //   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE [--resolve RESIDUAL]]
 //            [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]
+//            [--clade-idx N]
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
@@ -40,6 +41,20 @@
 //                                          line, the peaks (ascending) then the neighbours (ascending).  --assign reads it.
 //         <outdir>/peak_reads.csv          one row per peak in the order it was chosen: id,reads,degree,step -- the reads
 //                                          the loop removed for it, the sum of their degrees, the step that chose it.
+// --clade-idx N (with --assign only): the text behind the first tab or comma of every line of FILE is the haplotype's
+// abundance (strtod; a missing or unparsable value is an error), and the selection is named by lineage from annotation
+// column N of the MAT (arena::dump_haplotype_proportion / dump_lineage_proportion, arena.cpp:446-492, :530-588):
+//         <outdir>/haplotype_proportion.csv  one row per selected haplotype in the order of FILE: id,lineage,abundance
+//                                          (std::to_string).  The lineage is the first annotation on the way from the
+//                                          first source node of the condensed node to the root, then "/" + annotation
+//                                          for every further source node that is itself annotated (arena.cpp:462-483).
+//         <outdir>/lineage_proportion.csv  one row per lineage: lineage,sum of its haplotypes' abundances, accumulated
+//                                          in the order of FILE; rows by descending sum.  The reference's std::sort
+//                                          compares the sums only and leaves ties in the order of its hash map: here
+//                                          equal sums go by ascending name.
+// N beyond the last column prints the reference's error line (arena.cpp:458): the lineage column stays empty and
+// lineage_proportion.csv has no rows.  With --dump, --clade-idx prints `lineage <haplotype>\t<name>` for every haplotype.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -52,6 +67,7 @@
 int main(int argc, char** argv) {
     std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, neighbors_f, outdir = ".";
     int device = 0, radius = 2, max_neighbors = 500;       // config.hpp:24-25
+    int clade_idx = -1;                                     // --clade-idx: -1 = not given
     peaks_params peak_par;
     bool dump = false, want_peaks = false;
     for (int i = 1; i < argc; i++) {
@@ -75,14 +91,25 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--top-n")) peak_par.top_n = atoi(need("--top-n"));
         else if (!strcmp(argv[i], "--max-peaks")) peak_par.max_peaks = atoi(need("--max-peaks"));
         else if (!strcmp(argv[i], "--peak-radius")) peak_par.peak_radius = atoi(need("--peak-radius"));
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]\n"); return 1; }
+        else if (!strcmp(argv[i], "--clade-idx")) {
+            const char* v = need("--clade-idx");
+            char* endp = nullptr;
+            const long n = strtol(v, &endp, 10);
+            if (endp == v || *endp != '\0' || n < 0 || n > 1000000) { fprintf(stderr, "ERROR: --clade-idx needs a column number (0, 1, ...), got '%s'\n", v); return 1; }
+            clade_idx = (int)n;
+        }
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N]\n");
         return 1;
     }
     if (!resolve_f.empty() && assign_f.empty()) {
         fprintf(stderr, "ERROR: --resolve needs --assign: residual mutations are attributed to the selected haplotypes\n");
+        return 1;
+    }
+    if (clade_idx >= 0 && assign_f.empty() && !dump) {
+        fprintf(stderr, "ERROR: --clade-idx needs --assign: FILE names the haplotypes and their abundances\n");
         return 1;
     }
     if (radius < 0 || max_neighbors < 1) {
@@ -104,7 +131,25 @@ int main(int argc, char** argv) {
         std::unordered_map<MAT::Node*, std::vector<MAT::Node*>> mappings;
         MAT::Tree condensed = create_condensed_tree(T.root, site_read_map(reads, mask), mappings);
         fprintf(stderr, "%zu reads, %zu nodes, %zu haplotypes after condensing\n", reads.size(), T.size(), condensed.size());
+        // the lineage of a condensed node in annotation column clade_idx (arena.cpp:462-483)
+        const int max_clades_idx = (int)T.get_num_annotations() - 1;
+        auto lineage_of = [&](MAT::Node* hap) {
+            std::string name;
+            const std::vector<MAT::Node*>& sources = mappings[hap];
+            if (sources.empty()) return name;
+            auto own = [&](const MAT::Node* n) -> const std::string& {
+                static const std::string none;
+                return n->clade_annotations.size() > (size_t)clade_idx ? n->clade_annotations[(size_t)clade_idx] : none;
+            };
+            for (const MAT::Node* anc = sources.front(); anc; anc = anc->parent)
+                if (!own(anc).empty()) { name = own(anc); break; }
+            for (size_t i = 1; i < sources.size(); i++)
+                if (!own(sources[i]).empty()) name += "/" + own(sources[i]);
+            return name;
+        };
         if (dump) {
+            if (clade_idx >= 0 && clade_idx <= max_clades_idx)
+                for (MAT::Node* n : condensed.depth_first_expansion()) printf("lineage %s\t%s\n", n->identifier.c_str(), lineage_of(n).c_str());
             for (auto& r : reads) {
                 printf("read %s %d %d %d", r.read.c_str(), r.start, r.end, r.degree);
                 for (auto& m : r.mutations) printf(" %d:%d:%d", m.position, (int)m.ref_nuc, (int)m.mut_nuc);
@@ -120,7 +165,8 @@ int main(int argc, char** argv) {
             return 0;
         }
         // the selections are checked before the device is touched
-        auto read_selection = [&](const std::string& file, std::vector<MAT::Node*>& nodes, std::vector<std::string>& ids) -> bool {
+        auto read_selection = [&](const std::string& file, std::vector<MAT::Node*>& nodes, std::vector<std::string>& ids,
+                                  std::vector<double>* abundance = nullptr) -> bool {
             std::ifstream in(file);
             if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", file.c_str()); return false; }
             std::unordered_set<MAT::Node*> seen;
@@ -128,8 +174,16 @@ int main(int argc, char** argv) {
             std::string line;
             while (std::getline(in, line)) {
                 if (!line.empty() && line.back() == '\r') line.pop_back();
-                line = line.substr(0, line.find_first_of("\t,"));
+                const size_t cut = line.find_first_of("\t,");
+                const std::string tail = cut == std::string::npos ? std::string() : line.substr(cut + 1);
+                line = line.substr(0, cut);
                 if (line.empty()) continue;
+                if (abundance) {
+                    char* endp = nullptr;
+                    const double v = strtod(tail.c_str(), &endp);
+                    if (endp == tail.c_str()) { fprintf(stderr, "ERROR: %s: no abundance behind %s (--clade-idx reads one per line)\n", file.c_str(), line.c_str()); return false; }
+                    abundance->push_back(v);
+                }
                 MAT::Node* n = condensed.get_node(line);
                 if (!n && line.size() <= 9 && line.find_first_not_of("0123456789") == std::string::npos) {
                     if (arena.empty()) arena = condensed.depth_first_expansion();   // arena::from_mat, arena.cpp:3-55
@@ -146,7 +200,8 @@ int main(int argc, char** argv) {
         };
         std::vector<MAT::Node*> selected, pivots;
         std::vector<std::string> selected_ids, pivot_ids;
-        if (!assign_f.empty() && !read_selection(assign_f, selected, selected_ids)) return 1;
+        std::vector<double> abundance;
+        if (!assign_f.empty() && !read_selection(assign_f, selected, selected_ids, clade_idx >= 0 ? &abundance : nullptr)) return 1;
         if (!neighbors_f.empty() && !read_selection(neighbors_f, pivots, pivot_ids)) return 1;
         // so is the residual list
         std::vector<residual_mutation> residual;
@@ -209,6 +264,31 @@ int main(int argc, char** argv) {
             if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
             for (size_t k = 0; k < selected.size(); k++)
                 fprintf(f, "%s,%s\n", selected_ids[k].c_str(), std::to_string(asg.coverage[k]).c_str());   // arena.cpp:681-688
+            fclose(f);
+        }
+        if (clade_idx >= 0 && !selected.empty()) {
+            const bool in_range = clade_idx <= max_clades_idx;
+            if (!in_range) fprintf(stderr, "\n\nERROR: CLADE_IDX = %d exceeds Max CLADE_IDX = %d in the MAT!!!\n\n", clade_idx, max_clades_idx);   // arena.cpp:458
+            f = fopen((outdir + "/haplotype_proportion.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            std::vector<std::pair<std::string, double>> lineages;             // in order of first appearance: the sums add up in FILE order
+            std::unordered_map<std::string, size_t> lineage_at;
+            for (size_t k = 0; k < selected.size(); k++) {
+                const std::string name = in_range ? lineage_of(selected[k]) : std::string();
+                fprintf(f, "%s,%s,%s\n", selected_ids[k].c_str(), name.c_str(), std::to_string(abundance[k]).c_str());   // arena.cpp:488
+                auto at = lineage_at.emplace(name, lineages.size());
+                if (at.second) lineages.emplace_back(name, 0.0);
+                lineages[at.first->second].second += abundance[k];
+            }
+            fclose(f);
+            f = fopen((outdir + "/lineage_proportion.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            if (in_range) {
+                std::sort(lineages.begin(), lineages.end(), [](const auto& a, const auto& b) {
+                    return a.second > b.second || (a.second == b.second && a.first < b.first);
+                });
+                for (auto& l : lineages) fprintf(f, "%s,%s\n", l.first.c_str(), std::to_string(l.second).c_str());   // arena.cpp:580-585
+            }
             fclose(f);
         }
         if (!resolve_f.empty()) {

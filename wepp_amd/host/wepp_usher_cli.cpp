@@ -15,16 +15,17 @@
 
 static void usage() {
     fprintf(stderr, "usage: wepp-usher -i <mat.pb[.gz]> -v <samples.vcf[.gz]> [-d <outdir>] [-p] [-e max_uncertainty] "
-                    "[-E max_parsimony] [-s|-S|-A] [-r] [--device N | --devices 0,1,...] [--dump] [--report]\n"
+                    "[-E max_parsimony] [-s|-S|-A] [-r] [-D] [--device N | --devices 0,1,...] [--dump] [--report]\n"
                     "       --report prints one JSON line to stdout: seconds per phase (load, VCF, tree description, flatten, upload, "
                     "placement, writers), full flattens, peak resident memory\n"
+                    "       -D/--detailed-clades adds to clades.txt, per annotation column, the clades of all parsimony-optimal placements\n"
                     "       -n/--no-add is required: samples are placed on the tree as given, never added to it\n");
 }
 
 int main(int argc, char** argv) {
     std::string pb, vcf, outdir = ".";
     bool print_scores = false, dump = false, sort1 = false, sort2 = false, sort3 = false, reverse_sort = false;
-    bool no_add = false, report = false, load_only = false;
+    bool no_add = false, report = false, load_only = false, detailed_clades = false;
     std::vector<int> devices;
     uint32_t max_uncertainty = 1000000, max_parsimony = 1000000;   // usher.cpp:77-80 defaults
     int device = 0;
@@ -42,6 +43,7 @@ int main(int argc, char** argv) {
         else if (a == "-S" || a == "--sort-before-placement-2") sort2 = true;
         else if (a == "-A" || a == "--sort-before-placement-3") sort3 = true;
         else if (a == "-r" || a == "--reverse-sort") reverse_sort = true;
+        else if (a == "-D" || a == "--detailed-clades") detailed_clades = true;
         else if (a == "--device") device = atoi(next());
         else if (a == "--devices") {                              // one host thread + one handle per listed GPU
             std::vector<std::string> ids;
@@ -77,6 +79,14 @@ int main(int argc, char** argv) {
                 for (auto& m : n->mutations) printf(" %d:%d:%d:%d", m.position, m.ref_nuc, m.par_nuc, m.mut_nuc);
                 printf("\n");
             }
+            if (T.get_num_annotations() > 0) {       // the annotation columns, tab-separated (a name may hold blanks)
+                printf("annotations %zu\n", T.get_num_annotations());
+                for (auto n : bfs) {
+                    printf("clade %s", n->identifier.c_str());
+                    for (auto& a : n->clade_annotations) printf("\t%s", a.c_str());
+                    printf("\n");
+                }
+            }
             for (auto& s : missing_samples) {
                 printf("sample %s", s.name.c_str());
                 for (auto& m : s.mutations) printf(" %d:%d:%d:%d", m.position, m.ref_nuc, m.mut_nuc, (int)m.is_missing);
@@ -97,7 +107,7 @@ int main(int argc, char** argv) {
         }
         if (devices.empty()) devices.push_back(device);
         const int rc = usher_place_samples(outdir, max_uncertainty, max_parsimony, print_scores, missing_samples, low_conf, &T,
-                                           devices, nullptr, sort1, sort2, sort3, reverse_sort);
+                                           devices, nullptr, sort1, sort2, sort3, reverse_sort, detailed_clades);
         if (report) {
             struct rusage ru{};
             getrusage(RUSAGE_SELF, &ru);
