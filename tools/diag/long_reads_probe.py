@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """configs[4]'s shard (125 000 reads of 1.2 kb, device-resident) under several settings of the environment knobs of
-one handle each on the same flat image: tools/diag/long_reads_probe.py "WEPP_TARGET_WAVES_DENSE=8192" "WEPP_WINDOWS_UNFUSED=1" ...
+one handle each on the same flat image: tools/diag/long_reads_probe.py "WEPP_SCATTER_BLIND=1" "WEPP_WALK_MAX_EVENTS=16 WEPP_STEP_GROUPS=0" ...
 (an empty string = the defaults).  PROBE_NODES (16000000), PROBE_READS (125000)."""
 import os, sys, time
 import numpy as np

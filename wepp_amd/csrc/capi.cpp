@@ -47,7 +47,6 @@ void release(wepp_mat* h) {
     if (h->io_in) (void)hipFree(h->io_in);
     if (h->io_out) (void)hipFree(h->io_out);
     if (h->pin) (void)hipHostFree(h->pin);
-    if (h->epp_ws) (void)hipFree(h->epp_ws);
     if (h->d_work) (void)hipFree(h->d_work);
     for (uint32_t i = 0; i < wepp_mat::kRing; i++) {
         if (h->ev0[i]) (void)hipEventDestroy(h->ev0[i]);
@@ -123,13 +122,13 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     UP(d.maxnest, f.maxnest)
     UP(h->epp_word, f.epp_word) UP(h->epp_node, f.epp_node)
     h->epp_events = f.epp_word.size();
-    auto up_stream = [&](const Stream& st, uint32_t tier, bool eager, DevStream& ds) -> int {
+    auto up_stream = [&](const Stream& st, uint32_t tier, DevStream& ds) -> int {
         ds = DevStream{};
         ds.n = st.n;
         ds.NB = st.NB;
         ds.cp_stride = st.cp_stride;
         ds.ncp = (uint32_t)st.cp_off.size() - 1;
-        ds.eager = eager ? 1u : 0u;
+        ds.eager = 1u;                 // (crown and window streams; the whole-tree stream clears it below)
         ds.tier = tier;
         ds.e_pad = (uint32_t)st.E;
         UP(ds.nkey, st.nkey) UP(ds.nstat, st.nstat) UP(ds.blk_node0, st.blk_node0) UP(ds.blk_eoff, st.blk_eoff)
@@ -148,7 +147,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     };
     for (size_t i = 0; i < f.wstreams.size(); i++) {
         DevStream ds;
-        if ((rc = up_stream(f.wstreams[i], (uint32_t)(f.streams.size() - 1), h->tun.win_eager, ds)) != WEPP_OK) return rc;
+        if ((rc = up_stream(f.wstreams[i], (uint32_t)(f.streams.size() - 1), ds)) != WEPP_OK) return rc;
         h->wstreams.push_back(ds);
         h->wstream_bytes.push_back(f.wstreams[i].stream_bytes());
         if (i < MAX_WINDOWS) d.win_n[i] = f.wstreams[i].ncnt.empty() ? f.wstreams[i].n : 0xFFFFFFFFu;   // (pseudo-nodes: the whole tree)
@@ -161,7 +160,8 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     for (size_t i = 0; i < f.streams.size(); i++) {
         const Stream& st = f.streams[i];
         DevStream ds;
-        if ((rc = up_stream(st, (uint32_t)i, i + 1 < f.streams.size(), ds)) != WEPP_OK) return rc;
+        if ((rc = up_stream(st, (uint32_t)i, ds)) != WEPP_OK) return rc;
+        if (i + 1 == f.streams.size()) ds.eager = 0u;      // the whole tree prunes with the block minimum
         h->streams.push_back(ds);
         h->stream_bytes.push_back(st.stream_bytes());
         h->walks.push_back(DevWalk{});      // (a view into the walk arena, filled in below)
@@ -510,8 +510,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         // (the plain walks of this call may already run on their side stream, out of the lists in this workspace)
         if (L.ws) {
             HIP_TRY(hipStreamSynchronize(stream));
-            HIP_TRY(hipStreamSynchronize(L.side[MAX_STREAMS - 1]));
-            for (uint32_t i : {MAX_STREAMS - 6, MAX_STREAMS - 7, MAX_STREAMS - 3, MAX_STREAMS - 2}) HIP_TRY(hipStreamSynchronize(L.side[i]));
+            for (uint32_t i : {SIDE_WAVE, SIDE_WALK16, SIDE_PLAN, SIDE_JOBS16, SIDE_JOBS8}) HIP_TRY(hipStreamSynchronize(L.side[i]));
             (void)hipFree(L.ws);
             L.ws = nullptr;
             L.ws_bytes = 0;
@@ -525,19 +524,17 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         ws_moved = true;
         return WEPP_OK;
     };
-    const size_t tier_bytes = 0;       // (the plan ids live in mat->d_plan_of)
-    const size_t list_bytes = (((size_t)n_reads * 4) + 255) & ~(size_t)255;
+    const size_t list_bytes = (((size_t)n_reads * 4) + 255) & ~(size_t)255;      // (the plan ids live in mat->d_plan_of)
     const PlaceTunables& tun = mat->tun;
-    const bool sort_reads = tun.sort_reads;   // (WEPP_SORT_READS=0, an A/B aid: keep the caller's read order on the whole-tree stream too)
     size_t sort_temp = 0;
-    if (sort_reads) HIP_TRY(sort_reads_temp_bytes(n_reads, &sort_temp));
+    HIP_TRY(sort_reads_temp_bytes(n_reads, &sort_temp));
     sort_temp = (sort_temp + 255) & ~(size_t)255;
     // fixed part of the workspace: list | root_score | slot in block | jobs | sort keys in/out | sorted lists |
     // sort temp of the whole-tree plan and of the four walk classes (their sorts run on different side streams)
     constexpr uint32_t N_SORTS = 5;
     // (+ the chunked walk classes sized blind: first job of a read, and per class its reads, its job table, three partials per job)
     constexpr size_t blind_bytes = 2 * ((size_t)BLIND_CHUNKED_READS * 4 + (size_t)BLIND_JOB_CAP * 16);
-    const size_t fixed_bytes = tier_bytes + 8 * list_bytes + blind_bytes + (sort_reads ? 3 * list_bytes + N_SORTS * sort_temp : 0);
+    const size_t fixed_bytes = 11 * list_bytes + blind_bytes + N_SORTS * sort_temp;      // (8 lists of carve() + key_in, key_out, val_in)
     {
         // before routing only the fixed regions are needed; reserve a typical partial size too
         int rc = grow(fixed_bytes + (size_t)n_reads * 12 * 2);
@@ -573,34 +570,29 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             b_pc[cc] = (uint32_t*)p; p += (size_t)BLIND_JOB_CAP * 4;
         }
         wsid = mat->d_wsid_of + plan_base;
-        if (sort_reads) {
-            key_in = (uint32_t*)p; p += list_bytes;
-            key_out = (uint32_t*)p; p += list_bytes;
-            val_in = (uint32_t*)p; p += list_bytes;   // the sorted lists (same offsets as in `list`)
-            sort_tmp = p;                             // N_SORTS regions of sort_temp bytes
-        }
+        key_in = (uint32_t*)p; p += list_bytes;
+        key_out = (uint32_t*)p; p += list_bytes;
+        val_in = (uint32_t*)p; p += list_bytes;   // the sorted lists (same offsets as in `list`)
+        sort_tmp = p;                             // N_SORTS regions of sort_temp bytes
     };
     carve();
     uint32_t* tier_info = L.d_info + L.info_idx * TI_WORDS;
     uint32_t* blk_counts = L.d_info + 2 * TI_WORDS;
 
-    // events per job of the two chunked classes: WEPP_WALK_JOB_EVENTS fixes them, else they follow the handle's
-    // traffic (device_mat.hpp: WALK_TARGET_JOBS)
-    const uint32_t job_events = tun.job_events ? (tun.job_events | (tun.job_events << 16)) : (mat->job_events[0] | (mat->job_events[1] << 16));
-    const uint32_t walk_max_events = tun.walk_max_events, stack8 = tun.stack8, stack16 = tun.stack16;
+    // events per job of the two chunked classes: they follow the handle's traffic (device_mat.hpp: WALK_TARGET_JOBS)
+    const uint32_t job_events = mat->job_events[0] | (mat->job_events[1] << 16);
+    const uint32_t walk_max_events = tun.walk_max_events;
     // whole-genome samples are seeded (seed_kernels.hip) when work skipping is on and the tree carries signatures
     const uint32_t seed_min_hard = (mat->use_seeds && mat->use_crowns && mat->dev.seed_chunks) ? tun.seed_min_hard : 0xFFFFFFFFu;
     // ---- route the reads to streams ------------------------------------------------------
     const uint32_t ev_slot = (uint32_t)(mat->n_timed.fetch_add(1, std::memory_order_relaxed) % wepp_mat::kRing);
-    constexpr uint32_t BLIND16_STREAM = MAX_STREAMS - 6;     // (side stream of the second plain walk class)
-    constexpr uint32_t PLAN_STREAM = MAX_STREAMS - 7;
-    // Streams of a call.  The caller's stream runs k_route and, right behind it (no cross-stream wait: ~25 us), the
+    // Streams of a call (handle.hpp: SIDE_*).  The caller's stream runs k_route and, right behind it (no cross-stream wait: ~25 us), the
     // chunked walks of the first class -- the longest chain of the common case; the plain walks and the second chunked
     // class start from the routing kernel's event on side streams; everything the HOST has to size -- the counters'
     // copy, k_scatter, the sweeps, the planned walks -- lives on the plan stream `ps`, off the walks' path.  What ran
     // there behind the copy joins the caller's stream at the end; a call that launched nothing there joins nothing.
     const bool walking = mat->use_walk && walk_max_events;
-    hipStream_t ps = walking ? L.side[PLAN_STREAM] : stream;
+    hipStream_t ps = walking ? L.side[SIDE_PLAN] : stream;
     // WEPP_STEP_UNFUSED=1 (A/B aid): the launches behind k_route as they were before k_step -- the plain walks, k_walk_wave
     // on a side stream, the 8-entry job class blind on another, forked from an event of their own; results are identical
     const bool step_unfused = tun.step_unfused;
@@ -629,25 +621,27 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         return launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps);
     };
     // one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
-    auto blind_class = [&](uint32_t cls, hipStream_t q, bool fork_q) -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (fork_q) e = hipStreamWaitEvent(q, fork_from, 0);
-        if (e != hipSuccess) return e;
+    auto blind_class = [&](uint32_t cls, hipStream_t q) -> hipError_t {
         if (cls == PLAN_WALK8 || cls == PLAN_WALK16) {
-            e = launch_walk_blind(mat->dev, cls, cls == PLAN_WALK8 ? stack8 : stack16, n_reads, wlist[cls], tier_info + TI_WCUR + cls, d_read_off, d_read_word,
+            return launch_walk_blind(mat->dev, cls, cls == PLAN_WALK8 ? WALK8_ROWS : WALK16_ROWS, n_reads, wlist[cls], tier_info + TI_WCUR + cls, d_read_off, d_read_word,
                                   root_score, d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, q);
-        } else {
-            const uint32_t cc = cls - PLAN_WALKC8;
-            WalkJobs jb{};
-            jb.job_first = b_first;
-            jb.skip = tier_info + TI_JOVER + cc;
-            jb.job_n = job_n;
-            jb.part_score = b_ps[cc];
-            jb.part_rank = b_pr[cc];
-            jb.part_cnt = b_pc[cc];
-            e = launch_walk_jobs_blind(mat->dev, cls, cc ? stack16 : stack8, jb, b_jobs[cc], tier_info + TI_JCUR + cc, b_clist[cc], tier_info + TI_CCUR + cc,
-                                       d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, q);
         }
+        const uint32_t cc = cls - PLAN_WALKC8;
+        WalkJobs jb{};
+        jb.job_first = b_first;
+        jb.skip = tier_info + TI_JOVER + cc;
+        jb.job_n = job_n;
+        jb.part_score = b_ps[cc];
+        jb.part_rank = b_pr[cc];
+        jb.part_cnt = b_pc[cc];
+        return launch_walk_jobs_blind(mat->dev, cls, cc ? WALK16_ROWS : WALK8_ROWS, jb, b_jobs[cc], tier_info + TI_JCUR + cc, b_clist[cc], tier_info + TI_CCUR + cc,
+                                      d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, q);
+    };
+    // ... on side stream i, forked from the event behind k_route and joined into the caller's stream at the end of the call
+    auto blind_side = [&](uint32_t cls, uint32_t i) -> hipError_t {
+        hipError_t e = hipStreamWaitEvent(L.side[i], fork_from, 0);
+        if (e == hipSuccess) e = blind_class(cls, L.side[i]);
+        if (e == hipSuccess) e = hipEventRecord(L.join_ev[i], L.side[i]);
         return e;
     };
     const bool ww_jobs = mat->ww_by_jobs.load(std::memory_order_relaxed) != 0;     // (the reads with 17 - 256 events: a wave each, or jobs -- by the handle's previous call)
@@ -666,7 +660,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (walking) direct = RouteDirect{{wlist[0], wlist[1]}, {b_clist[0], b_clist[1]}, {b_jobs[0], b_jobs[1]}, b_first, wwlist,
                                           d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, walk_max_events,
                                           tun.ww_fixed ? tun.ww_block_max_small : ww_jobs ? 0u : 0xFFFFFFFFu, tun.ww_fixed ? tun.ww_block_max_big : ww_jobs ? 0u : 0xFFFFFFFFu};
-        HIP_TRY(launch_route(mat->dev, d_read_off, d_read_word, n_reads, mat->use_crowns, walking ? walk_limit : 0u, job_events, stack8, stack16, seed_min_hard, tun.seed_min_nodes, job_n, tier_of, root_score, blk_counts,
+        HIP_TRY(launch_route(mat->dev, d_read_off, d_read_word, n_reads, mat->use_crowns, walking ? walk_limit : 0u, job_events, WALK8_ROWS, WALK16_ROWS, seed_min_hard, tun.seed_min_nodes, job_n, tier_of, root_score, blk_counts,
                              tier_info, slot_in_blk, tier_info_next, wsid, direct, stream));
         L.info_idx ^= 1u;
         HIP_TRY(hipEventRecord(mat->ev0[ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
@@ -682,12 +676,12 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             // say they hold reads (blind_class below): two launches sized for a million reads that find a handful cost
             // ~20 us of workgroup dispatch each, and eight API calls per device call.
             if (step_unfused) {
-                HIP_TRY(blind_class(PLAN_WALK8, stream, false));
-                hipStream_t q = L.side[MAX_STREAMS - 1];
+                HIP_TRY(blind_class(PLAN_WALK8, stream));
+                hipStream_t q = L.side[SIDE_WAVE];
                 HIP_TRY(hipStreamWaitEvent(q, fork_from, 0));
                 HIP_TRY(launch_walk_wave(mat->dev, wwlist, tier_info + TI_WWCUR, n_reads, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best,
                                          d_flags, mat->d_work, wsid, q));
-                HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 1], q));
+                HIP_TRY(hipEventRecord(L.join_ev[SIDE_WAVE], q));
             } else {
                 // (wwlist also takes the few walkers of 9 - 16 entries k_route moves there, TI_W16WAVE, whatever the hint
                 // ww_by_jobs says: k_step reads the lists' cursors, and is the plain blind walk when they are empty)
@@ -701,21 +695,11 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                 const bool few = mat->step_walkers.load(std::memory_order_relaxed) <= STEP_GROUPS_MAX_WALKERS;
                 const uint32_t group = (!tun.step_groups || !few || walk_limit > 16u) ? 0u : walk_limit > 8u ? 16u : 8u;
                 if (tun.debug_plans) fprintf(stderr, "[step] walkers by groups of %u lanes (0: lane = read); plain walkers of the previous call: %u\n", group, mat->step_walkers.load(std::memory_order_relaxed));
-                HIP_TRY(launch_step(mat->dev, group, stack8, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
+                HIP_TRY(launch_step(mat->dev, group, WALK8_ROWS, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
                                     d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream));
             }
-            if (jobs8_blind) {
-                // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
-                hipStream_t q2 = L.side[MAX_STREAMS - 2];
-                HIP_TRY(blind_class(PLAN_WALKC8, q2, true));
-                HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 2], q2));
-            }
-            if (tun.blind16) {
-                // ... and the plain walks of 9 - 16 entries on a stream of their own: launched once the counters have
-                // reached the host they started when the walks of 1 - 8 entries ended, ~15 us of a 170 us step
-                HIP_TRY(blind_class(PLAN_WALK16, L.side[BLIND16_STREAM], true));
-                HIP_TRY(hipEventRecord(L.join_ev[BLIND16_STREAM], L.side[BLIND16_STREAM]));
-            }
+            // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
+            if (jobs8_blind) HIP_TRY(blind_side(PLAN_WALKC8, SIDE_JOBS8));
             HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
             // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
             // below), so their copy goes directly behind the wait, in front of any k_scatter, and an event of its own
@@ -773,7 +757,6 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
                 n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
                 info[TI_CCUR + 1], info[TI_JCUR], info[TI_JCUR + 1], info[TI_JOVER], info[TI_JOVER + 1]);
-    const bool blind_walks = walking;       // (launched behind k_route, joined below)
     // Who reads `list`: decided HERE, from the counters, for the whole call.  A plan with reads is a consumer unless its
     // class is placed out of k_route's own tables: the plain walk classes always, a chunked class that fitted its blind
     // tables (TI_JOVER == 0: launched blind or from the counters below, never by a plan of the host).
@@ -820,15 +803,15 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     }
     mat->step_walkers.store(info[TI_WCUR], std::memory_order_relaxed);      // (how the NEXT call's k_step places its plain walkers)
     bool late16[2] = {false, false}, late8 = false;
-    if (blind_walks) {
+    if (walking) {
+        // (the walks launched behind k_route are joined into the caller's stream below)
         // the 8-entry job class when the hint did not expect it, and the hint of the next call
         const bool jobs8 = info[TI_CCUR] && !info[TI_JOVER];
-        if (jobs8 && !jobs8_blind) { HIP_TRY(blind_class(PLAN_WALKC8, L.side[MAX_STREAMS - 2], true)); HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 2], L.side[MAX_STREAMS - 2])); late8 = true; }
+        if (jobs8 && !jobs8_blind) { HIP_TRY(blind_side(PLAN_WALKC8, SIDE_JOBS8)); late8 = true; }
         mat->expect_jobs8.store(jobs8 ? 1u : 0u, std::memory_order_relaxed);
         // the classes of 9 - 16 entries, from k_route's tables like the others, when they hold reads
-        if (tun.blind16) late16[0] = true;
-        else if (info[TI_WCUR + 1]) { HIP_TRY(blind_class(PLAN_WALK16, L.side[BLIND16_STREAM], true)); HIP_TRY(hipEventRecord(L.join_ev[BLIND16_STREAM], L.side[BLIND16_STREAM])); late16[0] = true; }
-        if (info[TI_CCUR + 1] && !info[TI_JOVER + 1]) { HIP_TRY(blind_class(PLAN_WALKC16, L.side[MAX_STREAMS - 3], true)); HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 3], L.side[MAX_STREAMS - 3])); late16[1] = true; }
+        if (info[TI_WCUR + 1]) { HIP_TRY(blind_side(PLAN_WALK16, SIDE_WALK16)); late16[0] = true; }
+        if (info[TI_CCUR + 1] && !info[TI_JOVER + 1]) { HIP_TRY(blind_side(PLAN_WALKC16, SIDE_JOBS16)); late16[1] = true; }
     }
     // ---- plan the launches ---------------------------------------------------------
     struct Plan { uint32_t t, count, off, T, ntiles, nchunks, bpc, ent_cap, key_cap, lds_bytes; bool s_in_lds, dense, window, win_table; size_t part_off; const uint32_t* lst; const DevStream* st; uint64_t sbytes; };
@@ -848,7 +831,9 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // the window plans share ONE launch (k_sweep_windows): their chunks are sized for the tiles of all of them together
     // (sized per plan, each window asked for enough waves to fill the chip on its own: 1.2 kb reads, 30 windows -- 9
     // workgroups per tile, each rebuilding the tile's table to sweep two blocks of the window's stream)
-    const bool fuse_windows = !tun.sweep_unfused && !tun.windows_unfused && mat->d_wstreams;
+    const bool fuse_windows = mat->d_wstreams != nullptr;
+    // the tile rule.  Reads per tile: at most MAX_TILE_ENTRIES read words per tile (long reads share a sweep between
+    // fewer reads), a power of two, never more than the knob; long reads take the dense (table) variant of the sweep
     auto tile_reads = [&](uint32_t maxk) { uint32_t Tp = T; while (Tp > 1 && (uint64_t)Tp * maxk > MAX_TILE_ENTRIES) Tp >>= 1; return Tp; };
     auto takes_table = [&](uint32_t maxk) { return maxk <= MAX_TILE_ENTRIES && maxk >= DENSE_MIN_READ_WORDS && mat->dev.max_pos <= DENSE_MAX_POS; };
     uint64_t win_tiles = 0;
@@ -878,7 +863,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             // the reads with many events: their walks are cut into jobs (below); the plans of a chunked class
             // are the streams, the jobs of stream t numbered behind those of the streams before it
             const uint32_t cc = cls - PLAN_WALKC8;
-            if (blind_walks && !info[TI_JOVER + cc]) { walk_reads += count; continue; }     // (launched blind behind k_route)
+            if (walking && !info[TI_JOVER + cc]) { walk_reads += count; continue; }     // (launched blind behind k_route)
             WalkPlans& wc = walkc[cc];
             WalkPlanDev& d = wc.p[wc.n];
             d.tier = t;
@@ -911,16 +896,13 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         p.sbytes = p.window ? mat->wstream_bytes[t] : mat->stream_bytes[t];
         p.count = count;
         p.off = info[TI_OFF + id];
-        // reads per tile: at most MAX_TILE_ENTRIES read words per tile (long reads share a
-        // sweep between fewer reads), a power of two, never more than the knob
         const uint32_t maxk = std::max<uint32_t>(1, info[TI_MAXK + id]);
-        uint32_t Tp = T;
-        while (Tp > 1 && (uint64_t)Tp * maxk > MAX_TILE_ENTRIES) Tp >>= 1;
+        const uint32_t Tp = tile_reads(maxk);
         p.T = Tp;
         p.ntiles = (count + Tp - 1) / Tp;
         // a read longer than MAX_TILE_ENTRIES words is swept alone with its words left in global memory
         p.s_in_lds = maxk <= MAX_TILE_ENTRIES;
-        p.dense = p.s_in_lds && maxk >= DENSE_MIN_READ_WORDS && mat->dev.max_pos <= DENSE_MAX_POS;
+        p.dense = takes_table(maxk);
         const uint64_t need = std::min<uint64_t>((uint64_t)std::min(Tp, count) * maxk, MAX_TILE_ENTRIES);
         const uint32_t cap = (uint32_t)((need + 63) & ~63ull);
         uint32_t kcap = 64;
@@ -934,18 +916,13 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         p.lds_bytes = p.s_in_lds ? sweep_lds_bytes(mat->dev.bm_words, cap, kcap, p.dense, p.win_table) : bm_bytes;
         // chunks: enough single-wave workgroups to fill 256 CUs, cut at checkpoints
         const DevStream& st = *p.st;
-        const uint32_t target_waves = tun.target_waves;   // 4096: 16 resident single-wave workgroups per CU x 256 CUs; 2048 / 8192 / 16384 measured slower (WEPP_TARGET_WAVES: tuning aid)
-        // (the 8-wave workgroups of the dense / window variant run for milliseconds: four times as many of them
-        // balance the chip better -- 1.2 kb reads 132 -> 120 ms per 200 K at 16384, the same at 32768)
-        const uint32_t target_waves_dense = tun.target_waves_dense;
-        uint32_t nchunks = std::max<uint32_t>(1, ((p.dense ? target_waves_dense : target_waves) + p.ntiles - 1) / p.ntiles);
-        if (p.win_table && fuse_windows) nchunks = std::max<uint32_t>(1, (uint32_t)((target_waves_dense + win_tiles - 1) / win_tiles));
+        uint32_t nchunks = std::max<uint32_t>(1, ((p.dense ? SWEEP_TARGET_WAVES_DENSE : SWEEP_TARGET_WAVES) + p.ntiles - 1) / p.ntiles);
+        if (p.win_table && fuse_windows) nchunks = std::max<uint32_t>(1, (uint32_t)((SWEEP_TARGET_WAVES_DENSE + win_tiles - 1) / win_tiles));
         // ... and chunks no longer than what stays in an XCD's L2 while the tiles sweep it: the waves of
         // a launch are ordered chunk-major (all tiles of chunk 0, then of chunk 1, ...), so the ~4 K
         // resident waves walk the same ~1.5 MB of the stream together instead of drifting apart over
         // 118 MB (whole-tree sweep of 1 M reads: 432 ms with one chunk per tile, 235 ms with 80)
-        const uint64_t chunk_bytes = tun.chunk_bytes;
-        nchunks = std::max<uint32_t>(nchunks, (uint32_t)((p.sbytes + chunk_bytes - 1) / chunk_bytes));
+        nchunks = std::max<uint32_t>(nchunks, (uint32_t)((p.sbytes + SWEEP_CHUNK_BYTES - 1) / SWEEP_CHUNK_BYTES));
         nchunks = std::min<uint32_t>(nchunks, (uint32_t)std::max<uint64_t>(1, SWEEP_MAX_PARTIAL_BYTES / ((uint64_t)count * 12)));
         // ... but a chunk's wave pays a set-up (bitmap, read words, checkpoint) worth several blocks: no chunk
         // shorter than 8 blocks, however few tiles the plan has (a plan of a few hundred reads used to be cut into
@@ -985,7 +962,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                     p.window ? "window" : "sweep", p.t, p.count, p.off, p.T, p.ntiles, p.nchunks, p.bpc, p.st->NB, p.st->ncp, (int)p.dense,
                     p.lds_bytes, p.ent_cap, p.key_cap, p.part_off);
         // the reads that sweep the whole tree go by first listed position (sort_reads.hip)
-        if (sort_reads && !p.window && p.t + 1 == ns && p.count >= SORT_MIN_READS) {
+        if (!p.window && p.t + 1 == ns && p.count >= SORT_MIN_READS) {
             HIP_TRY(launch_first_pos(list + p.off, p.count, d_read_off, d_read_word, key_in + p.off, ps));
             HIP_TRY(launch_sort_reads(key_in + p.off, key_out + p.off, list + p.off, val_in + p.off, p.count, sort_tmp, sort_temp, ps));
             p.lst = val_in + p.off;
@@ -996,7 +973,6 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // The plain (short-read) plans are fused into ONE launch, longest chunks first; dense
     // and out-of-LDS plans get their own launch on a side stream forked from / joined into
     // `stream`.  Every plan's finalize follows its sweep.
-    const uint32_t slot = ev_slot;
     uint64_t passes = 0, bytes = 0;
     auto parts = [&](const Plan& p, int32_t*& ps, uint32_t*& pr, uint32_t*& pc) {
         ps = (int32_t*)(part_base + p.part_off);
@@ -1004,12 +980,9 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         pc = pr + (size_t)p.nchunks * p.count;
     };
     uint32_t order[MAX_PLANS], n_plain = 0, n_other = 0, others[MAX_PLANS];
-    // WEPP_SWEEP_UNFUSED=1 (profiling aid): one launch per plan, back to back on `stream`, so that a
-    // kernel trace shows the time of every stream's sweep; results are identical
-    const bool unfused = tun.sweep_unfused;
     uint32_t wins[MAX_WINDOWS], n_wins = 0;
     for (uint32_t i = 0; i < np; i++) {
-        if (plans[i].s_in_lds && !plans[i].dense && !unfused && n_plain < MAX_STREAMS) order[n_plain++] = i;
+        if (plans[i].s_in_lds && !plans[i].dense && n_plain < MAX_STREAMS) order[n_plain++] = i;
         else if (plans[i].win_table && fuse_windows && n_wins < MAX_WINDOWS) wins[n_wins++] = i;
         else others[n_other++] = i;
         passes += plans[i].ntiles;                                   // every tile sweeps its stream once
@@ -1022,7 +995,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         passes += (info[TI_WCUR + cls] + 63) / 64;      // a walk "pass" = one wave of 64 reads
     passes += (info[TI_RESOLVED] + 63) / 64 + info[TI_WWCUR] + info[TI_WWCUR + 1];
     for (uint32_t cc = 0; cc < 2; cc++)
-        if (blind_walks && !info[TI_JOVER + cc]) {
+        if (walking && !info[TI_JOVER + cc]) {
             passes += (info[TI_JCUR + cc] + 63) / 64;
             bytes += (uint64_t)info[TI_CCUR + cc] * 40 + (uint64_t)info[TI_JCUR + cc] * 16;      // (job table, partials, the combination's reads and results)
         }
@@ -1030,21 +1003,27 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (walkc[cc].n) passes += walkc[cc].p[walkc[cc].n - 1].wave_end;
     const uint32_t n_walk_chains = (walkc[0].n || walkc[1].n) ? 1u : 0u;
     const uint32_t n_chains = n_other + n_walk_chains + (arena_n ? 1u : 0u) + (seed_n ? 1u : 0u) + (n_wins ? 1u : 0u);     // launch chains beside the fused plain sweeps
-    const bool fork = !unfused && (n_chains > 0) && (n_plain > 0 || n_chains > 1);
+    const bool fork = (n_chains > 0) && (n_plain > 0 || n_chains > 1);
     if (fork) HIP_TRY(hipEventRecord(L.fork_ev, ps));
-    // the side streams join the caller's stream only after everything has been launched: a join in between
-    // would make the launches behind it wait for the side stream's kernels
-    uint32_t joins[2 * MAX_STREAMS], n_joins = 0;     // (a stream may be listed twice: waiting twice for its event is harmless)
-    // side streams of the sweeps that are launched on their own (dense / window / out-of-LDS plans); the last
-    // three belong to the walks
-    constexpr uint32_t OTHER_SIDE_STREAMS = MAX_STREAMS - 3;
+    // A chain beside the fused sweeps runs on side stream i (handle.hpp: SIDE_*) when the call forks, else on ps.
+    // The side streams join ps only after everything has been launched: a join in between would make the launches
+    // behind it wait for the side stream's kernels.  join(): the chain's last launch is queued; its stream is listed once.
+    uint32_t joins[MAX_STREAMS], n_joins = 0;
+    auto fork_to = [&](uint32_t i, hipStream_t& q) -> hipError_t {
+        q = fork ? L.side[i] : ps;
+        return fork ? hipStreamWaitEvent(q, L.fork_ev, 0) : hipSuccess;
+    };
+    auto join = [&](uint32_t i) -> hipError_t {
+        if (!fork) return hipSuccess;
+        const hipError_t e = hipEventRecord(L.join_ev[i], L.side[i]);
+        if (e == hipSuccess && std::find(joins, joins + n_joins, i) == joins + n_joins) joins[n_joins++] = i;
+        return e;
+    };
     // A walk class's reads go by (stream, first listed position) when there are enough of them (device_mat.hpp:
-    // WALK_SORT_MIN_READS; WEPP_WALK_SORT=0: A/B aid): sorted on the class's own stream, right before its launch.
+    // WALK_SORT_MIN_READS): sorted on the class's own stream, right before its launch.
     // `region` = which of the sort temp regions (1..4; 0 is the whole-tree plan's).
-    const bool walk_sort = tun.walk_sort;
     auto sort_class = [&](uint32_t cls, uint32_t region, hipStream_t q, bool& sorted) -> int {
         sorted = false;
-        if (!walk_sort) return WEPP_OK;
         const uint32_t off = info[TI_OFF + plan_id(cls, 0)];
         const uint32_t cnt = info[TI_OFF + plan_id(cls, 0) + MAX_STREAMS] - off;      // (plan ids of a class are consecutive)
         if (cnt < WALK_SORT_MIN_READS) return WEPP_OK;
@@ -1079,10 +1058,8 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             for (uint32_t cc = 0; cc < 2; cc++) {
                 if (!walkc[cc].n) continue;
                 // each class on a side stream of its own: a chain of short, latency-bound launches
-                if (fork) {
-                    q = L.side[MAX_STREAMS - 2 - cc];
-                    HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
-                }
+                const uint32_t side = cc ? SIDE_JOBS16 : SIDE_JOBS8;
+                HIP_TRY(fork_to(side, q));
                 const uint32_t R3 = walkc_reads[cc], J = (uint32_t)n_jobs[cc];
                 const size_t b_cnt = pad((size_t)R3 * 4), b_tmp = pad(scan_temp[cc]), b_job = pad((size_t)J * 4);
                 char* w2 = (char*)L.ws2 + base[cc];
@@ -1112,17 +1089,14 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                 HIP_TRY(launch_walk_jobs(mat->dev, walkc[cc], PLAN_WALKC8 + cc, info[TI_OPEN + 2 + cc], jb, d_read_off, d_read_word, root_score, mat->d_work, wsid, q));
                 HIP_TRY(launch_finalize_jobs(mat->dev, list3, R3, jb, d_read_off, d_read_word, d_best_bfs_j, d_score,
                                              d_num_best, d_flags, q));
-                if (fork) {
-                    HIP_TRY(hipEventRecord(L.join_ev[MAX_STREAMS - 2 - cc], q));
-                    joins[n_joins++] = MAX_STREAMS - 2 - cc;
-                }
+                HIP_TRY(join(side));
             }
         }
     }
     for (uint32_t k = 0; k < n_other; k++) {
         const Plan& p = plans[others[k]];
-        hipStream_t q = fork ? L.side[k % OTHER_SIDE_STREAMS] : ps;
-        if (fork) HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
+        hipStream_t q;
+        HIP_TRY(fork_to(k % OTHER_SIDE_STREAMS, q));
         int32_t* ps; uint32_t *pr, *pc;
         parts(p, ps, pr, pc);
         HIP_TRY(launch_sweep(mat->dev, *p.st, d_read_off, d_read_word, root_score, p.lst, p.count, p.T,
@@ -1130,11 +1104,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                              p.nchunks, p.bpc, p.s_in_lds, p.dense, p.win_table, p.ent_cap, p.key_cap, p.lds_bytes, ps, pr, pc, q));
         HIP_TRY(launch_finalize(mat->dev, d_read_off, d_read_word, p.lst, p.count, p.nchunks, ps, pr, pc,
                                 d_best_bfs_j, d_score, d_num_best, d_flags, q));
-        if (fork && (k + OTHER_SIDE_STREAMS >= n_other)) {
-            // the last launch on every side stream joins the caller's stream
-            HIP_TRY(hipEventRecord(L.join_ev[k % OTHER_SIDE_STREAMS], q));
-            joins[n_joins++] = k % OTHER_SIDE_STREAMS;
-        }
+        if (k + OTHER_SIDE_STREAMS >= n_other) HIP_TRY(join(k % OTHER_SIDE_STREAMS));     // (the last of these launches on its side stream)
     }
     if (n_wins) {
         // longest chunks first: the workgroups of the largest windows' streams start first
@@ -1155,50 +1125,35 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             lds_max = std::max(lds_max, p.lds_bytes);
         }
         pl.n = n_wins;
-        hipStream_t q = fork ? L.side[OTHER_SIDE_STREAMS - 3] : ps;
-        if (fork) HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
+        hipStream_t q;
+        HIP_TRY(fork_to(SIDE_WINDOWS, q));
         HIP_TRY(launch_sweep_windows(mat->dev, mat->d_wstreams, pl, d_read_off, d_read_word, root_score, lds_max, q));
         HIP_TRY(launch_finalize_windows(mat->dev, pl, d_read_off, d_read_word, d_best_bfs_j, d_score, d_num_best, d_flags, q));
-        if (fork) {
-            HIP_TRY(hipEventRecord(L.join_ev[OTHER_SIDE_STREAMS - 3], q));
-            bool listed = false;
-            for (uint32_t i = 0; i < n_joins; i++) listed = listed || joins[i] == OTHER_SIDE_STREAMS - 3;
-            if (!listed) joins[n_joins++] = OTHER_SIDE_STREAMS - 3;
-        }
+        HIP_TRY(join(SIDE_WINDOWS));
     }
     if (arena_n) {
         if (arena_maxk > MAX_TILE_ENTRIES) return set_error(WEPP_ELIMIT, "a read inside one genome window lists more than 8192 positions");
         const uint32_t cap = (arena_maxk + 63) & ~63u;
-        hipStream_t q = fork ? L.side[OTHER_SIDE_STREAMS - 1] : ps;      // (the last of the sweeps' side streams)
-        if (fork) HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
+        hipStream_t q;
+        HIP_TRY(fork_to(SIDE_ARENA, q));
         int32_t* ps = (int32_t*)(part_base + arena_part);
         uint32_t *pr = (uint32_t*)(ps + (size_t)arena_n * ARENA_CHUNKS), *pc = pr + (size_t)arena_n * ARENA_CHUNKS;
         HIP_TRY(launch_sweep_arena(mat->dev, mat->dev.wc_streams, wsid, d_read_off, d_read_word, root_score, list + arena_off, arena_n, cap,
                                    sweep_lds_bytes(mat->dev.bm_words, cap, 0, false), ps, pr, pc, q));
         HIP_TRY(launch_finalize(mat->dev, d_read_off, d_read_word, list + arena_off, arena_n, ARENA_CHUNKS, ps, pr, pc, d_best_bfs_j, d_score,
                                 d_num_best, d_flags, q));
-        if (fork) {
-            HIP_TRY(hipEventRecord(L.join_ev[OTHER_SIDE_STREAMS - 1], q));
-            bool listed = false;
-            for (uint32_t i = 0; i < n_joins; i++) listed = listed || joins[i] == OTHER_SIDE_STREAMS - 1;
-            if (!listed) joins[n_joins++] = OTHER_SIDE_STREAMS - 1;
-        }
+        HIP_TRY(join(SIDE_ARENA));
         passes += arena_n;
     }
     if (seed_n) {
         if (seed_maxk > SEED_MAX_ENTRIES) return set_error(WEPP_EDEVICE, "routing seeded a sample with too many entries");
         const uint32_t cap = (seed_maxk + 63) & ~63u;
-        hipStream_t q = fork ? L.side[OTHER_SIDE_STREAMS - 2] : ps;
-        if (fork) HIP_TRY(hipStreamWaitEvent(q, L.fork_ev, 0));
+        hipStream_t q;
+        HIP_TRY(fork_to(SIDE_SEED, q));
         if (debug_plans) fprintf(stderr, "[plan] seed count=%u maxk=%u chunks=%u lds=%u\n", seed_n, seed_maxk, mat->dev.seed_chunks, seed_lds_bytes(mat->dev, cap));
         HIP_TRY(launch_seed(mat->dev, mat->streams.back(), list + seed_off, seed_n, cap, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score,
                             d_num_best, d_flags, mat->d_work, tun.seed_heavy ? L.d_seed_heavy : nullptr, q));
-        if (fork) {
-            HIP_TRY(hipEventRecord(L.join_ev[OTHER_SIDE_STREAMS - 2], q));
-            bool listed = false;
-            for (uint32_t i = 0; i < n_joins; i++) listed = listed || joins[i] == OTHER_SIDE_STREAMS - 2;
-            if (!listed) joins[n_joins++] = OTHER_SIDE_STREAMS - 2;
-        }
+        HIP_TRY(join(SIDE_SEED));
         passes += seed_n;
     }
     if (n_plain) {
@@ -1228,19 +1183,19 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                                       ps));
     }
     for (uint32_t i = 0; i < n_joins; i++) HIP_TRY(hipStreamWaitEvent(ps, L.join_ev[joins[i]], 0));
-    if (blind_walks) {
+    if (walking) {
         // the plan stream, when something ran on it behind the counters' copy (k_scatter and what reads its lists: no
         // consumer is launched without it), and the blind walks' side streams join the caller's stream
         if (scattered) {
-            HIP_TRY(hipEventRecord(L.join_ev[PLAN_STREAM], ps));
-            HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[PLAN_STREAM], 0));
+            HIP_TRY(hipEventRecord(L.join_ev[SIDE_PLAN], ps));
+            HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_PLAN], 0));
         }
-        if (step_unfused) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 1], 0));
-        if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 2], 0));
-        if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[BLIND16_STREAM], 0));
-        if (late16[1]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[MAX_STREAMS - 3], 0));
+        if (step_unfused) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_WAVE], 0));
+        if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS8], 0));
+        if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_WALK16], 0));
+        if (late16[1]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS16], 0));
     }
-    HIP_TRY(hipEventRecord(mat->ev1[slot], stream));
+    HIP_TRY(hipEventRecord(mat->ev1[ev_slot], stream));
     {
         std::lock_guard<std::mutex> lk(mat->stat_mu);
         mat->last_passes = passes;

@@ -139,9 +139,8 @@ constexpr uint32_t WALK_JOB_EVENTS = 8;
 // whose start state (a third of a short job's cycles and bytes) is amortised, when it holds 10^8 events (tree-wide
 // walks of N-rich batches).  Speed only: results never depend on it.
 constexpr uint32_t WALK_JOB_EVENTS_MAX = 256, WALK_TARGET_JOBS = 1u << 20;
-// most stack rows a walk workgroup gets (<= WALK8_STACK / WALK16_STACK, what the kernels take; WEPP_WALK_STACK8 /
-// WEPP_WALK_STACK16 lower them): a read that could hold more intervals open at once (sum of ix_nest over its
-// positions) is left to the sweeps.  A launch asks LDS for the deepest stack its reads can need (k_route's maximum
+// most stack rows a walk workgroup gets (WALK8_ROWS / WALK16_ROWS <= WALK8_STACK / WALK16_STACK, what the kernels
+// take): a read that could hold more intervals open at once (sum of ix_nest over its positions) is left to the sweeps.  A launch asks LDS for the deepest stack its reads can need (k_route's maximum
 // per class), which on the synthetic SARS-CoV-2-like MAT is 17 (up to 8 entries) / 25 (9-16) of 200 K reads.
 // Measured (16 M nodes, 1 M reads with 5 % N): rows 16/32 -> 12/20 (2 -> 3.5 waves per SIMD for the 16-entry
 // class) 21.5 -> 19.9 ms, nothing on the other legs: the walks are not short of waves.
@@ -183,11 +182,7 @@ struct WalkPlans {
     uint32_t n;
     WalkPlanDev p[MAX_STREAMS];
 };
-// cls = 0 / 1: the plans of one class in ONE launch, a wave = 64 reads; writes the final per-read results
-hipError_t launch_walk(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const uint32_t* d_read_off,
-                       const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score,
-                       uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
-// the plain walks of one class sized BLIND: the reads are list[0 .. *count) (k_route's list and cursor, both on the device),
+// the plain walks of one class (cls = 0 / 1, a wave = 64 reads; writes the final per-read results) sized BLIND: the reads are list[0 .. *count) (k_route's list and cursor, both on the device),
 // the grid is the worst case (max_reads lanes), every read walks the arena slice wsid names; waves beyond the count leave
 hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, uint32_t max_reads, const uint32_t* list, const uint32_t* count,
                              const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
@@ -349,6 +344,10 @@ hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const uint32_t* d_
 #ifndef WEPP_SWEEP_WAVES
 #define WEPP_SWEEP_WAVES 1
 #endif
+// waves a plan's chunks aim at.  4096: 16 resident single-wave workgroups per CU x 256 CUs; 2048 / 8192 / 16384 measured
+// slower.  The 8-wave workgroups of the dense / window variant run for milliseconds: four times as many of them balance
+// the chip better -- 1.2 kb reads 132 -> 120 ms per 200 K at 16384, the same at 32768
+constexpr uint32_t SWEEP_TARGET_WAVES = 4096, SWEEP_TARGET_WAVES_DENSE = 16384;
 constexpr uint64_t SWEEP_CHUNK_BYTES = 1ull << 20;   // 1 MB of stream per chunk (an XCD's L2 holds 4 MB; 0.75 / 1 / 1.5 / 2 / 3 MB: 236 / 235 / 238 / 240 / 250 ms)
 constexpr uint64_t SWEEP_MAX_PARTIAL_BYTES = 16ull << 30;   // per-(chunk, read) partial results of one stream: chunks get longer beyond
 constexpr uint32_t SWEEP_WAVES = WEPP_SWEEP_WAVES;            // independent sweeps (waves) per workgroup of k_sweep_multi

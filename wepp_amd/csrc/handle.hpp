@@ -49,6 +49,22 @@ struct PlaceLane {
     void* d_seed_heavy = nullptr;
 };
 
+// Which of a lane's side streams (and join events, same index) a launch chain of place_device runs on.  The values are
+// the ones every measurement was taken with and must not change.  The plans launched on their own (dense, out-of-LDS,
+// window plans beyond MAX_WINDOWS) take side[k % OTHER_SIDE_STREAMS] in turn, so some streams serve twice: stream 10 is
+// the 16-entry plain walk class AND the fused window plans, stream 9 is the plan stream AND the tenth such plan (11 and
+// 12, seeds and arena, the twelfth and thirteenth).  Chains that share a stream run one behind the other, no more.
+constexpr uint32_t SIDE_WAVE = MAX_STREAMS - 1;        // k_walk_wave of WEPP_STEP_UNFUSED=1
+constexpr uint32_t SIDE_JOBS8 = MAX_STREAMS - 2;       // the 8-entry job class, blind or planned
+constexpr uint32_t SIDE_JOBS16 = MAX_STREAMS - 3;      // the 16-entry job class
+constexpr uint32_t SIDE_WALK16 = MAX_STREAMS - 6;      // the plain walks of 9 - 16 entries
+constexpr uint32_t SIDE_PLAN = MAX_STREAMS - 7;        // everything the host sizes: the counters' copy, k_scatter, the fused sweeps
+constexpr uint32_t OTHER_SIDE_STREAMS = MAX_STREAMS - 3;   // streams 0 .. 12: the plans launched on their own; the three behind them belong to the walks
+constexpr uint32_t SIDE_ARENA = OTHER_SIDE_STREAMS - 1;    // window-crown sweeps (k_sweep_arena)
+constexpr uint32_t SIDE_SEED = OTHER_SIDE_STREAMS - 2;     // whole-genome samples (k_seed)
+constexpr uint32_t SIDE_WINDOWS = OTHER_SIDE_STREAMS - 3;  // the fused window plans (k_sweep_windows)
+static_assert(SIDE_WALK16 == 10 && SIDE_WINDOWS == 10 && SIDE_PLAN == 9 && SIDE_SEED == 11 && SIDE_ARENA == 12, "the side streams keep their numbers");
+
 struct wepp_mat {
     static constexpr uint32_t kLanes = 2;
     int device = 0;
@@ -77,8 +93,6 @@ struct wepp_mat {
     const uint32_t* epp_word = nullptr;
     const uint32_t* epp_node = nullptr;
     uint64_t epp_events = 0;
-    void* epp_ws = nullptr;           // (unused)
-    size_t epp_ws_bytes = 0;
     // device buffers of wepp_epp_map kept between calls (gigabytes at 16 M nodes: a hipMalloc of that size costs
     // tens of milliseconds); a call takes the blocks that fit and hands everything back when it returns.  Freed
     // with the handle (release() has selected the device by then).

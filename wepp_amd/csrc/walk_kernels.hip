@@ -702,27 +702,6 @@ static uint32_t walk_lds_bytes(uint32_t kw, uint32_t sd_rows) { return WALK_WAVE
 // scratch, never more than the class admits
 static uint32_t walk_stack_rows(uint32_t open_max, uint32_t sd) { return std::min(sd, std::max(open_max, 2u)); }
 
-hipError_t launch_walk(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const uint32_t* d_read_off,
-                       const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score,
-                       uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
-    if (pl.n == 0) return hipSuccess;
-    const uint32_t waves = pl.p[pl.n - 1].wave_end;
-    const dim3 grid((waves + WALK_WAVES - 1) / WALK_WAVES), block(64 * WALK_WAVES);
-    const WalkJobs none{};
-    if (cls == PLAN_WALK8) {
-        const uint32_t sd = walk_stack_rows(open_max, WALK8_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK8_K, (int)WALK8_STACK, false>), grid, block, walk_lds_bytes(WALK8_K, sd), stream, m, pl,
-                           none, sd, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    } else {
-        const uint32_t sd = walk_stack_rows(open_max, WALK16_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK16_K, (int)WALK16_STACK, false>), grid, block, walk_lds_bytes(WALK16_K, sd), stream, m, pl,
-                           none, sd, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid,
-                           (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, uint32_t max_reads, const uint32_t* list, const uint32_t* count,
                              const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
                              int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid,
