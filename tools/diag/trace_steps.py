@@ -6,7 +6,7 @@ for f in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].split("::")[-1][:40]))
 rows.sort()
 # the steps: from a k_route to the next; the last 14 steps of the run (the timed loop is the end of the run, without legs)
-idx = [i for i, r in enumerate(rows) if r[2].startswith("k_route")]
+idx = [i for i, r in enumerate(rows) if r[2] == "k_route"]       # (not k_route_tables / k_route_pos: once per upload)
 steps = [(rows[a:b]) for a, b in zip(idx[:-1], idx[1:])][-15:-1]
 dur, gap_next, start_after = {}, [], {}
 for s, nxt in zip(steps, [x[0] for x in steps[1:]] + [None]):

@@ -242,12 +242,20 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
             return WEPP_OK;
         };
         IxHead* g_head; IxEnt* g_ent; uint8_t *g_nest, *g_sp; NodeRec* g_nrec; SegNode *g_pre, *g_suf, *g_dst;
+        uint32_t* g_rtpos;                         // k_route's word per head slot, derived from g_head and g_nest slice by slice (route_pos.hpp)
 #define ARR(ptr, count, front) if ((rc = dev_array(ptr, count, front)) != WEPP_OK) { release(h); return rc; }
         ARR(g_head, tot_head, a_head) ARR(g_ent, tot_ent, a_ent) ARR(g_nest, tot_head, a_nest) ARR(g_sp, tot_sp, a_sp)
         ARR(g_nrec, tot_n, a_nrec) ARR(g_pre, tot_n, a_pre) ARR(g_suf, tot_n, a_suf) ARR(g_dst, tot_dst, a_dst)
+        ARR(g_rtpos, tot_head, std::vector<uint32_t>())
 #undef ARR
         arena.ix_head = g_head; arena.ix_ent = g_ent; arena.ix_nest = g_nest; arena.sp = g_sp;
         arena.nrec = g_nrec; arena.rq_pre = g_pre; arena.rq_suf = g_suf; arena.rq_dst = g_dst;
+        d.rt_pos = g_rtpos;
+        for (size_t w = 0; w < f.wcrowns.size(); w++)
+            for (size_t i = 0; i < f.wcrowns[w].size(); i++) {
+                const WcInfo& wi = info[w * WC_MAX + i];
+                HIP_TRY(launch_route_pos(g_head + wi.head_off, g_nest + wi.nest_off, (uint32_t)f.wcrowns[w][i].ix_head.size(), g_rtpos + wi.head_off, nullptr));
+            }
         {
             size_t o_n = wc_n, o_ent = wc_ent, o_head = wc_head, o_sp = wc_sp, o_dst = wc_dst;
             for (size_t i = 0; i < f.streams.size(); i++) {
@@ -267,6 +275,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
                 CP(g_nrec, o_n, st.nrec) CP(g_pre, o_n, st.rq_pre) CP(g_suf, o_n, st.rq_suf) CP(g_dst, o_dst, st.rq_dst)
 #undef CP
                 if (o_ent) HIP_TRY(launch_rebase_index(g_head + o_head, (uint32_t)st.ix_head.size(), g_ent + o_ent, (uint32_t)st.ix_ent.size(), (uint32_t)o_ent, nullptr));
+                HIP_TRY(launch_route_pos(g_head + o_head, g_nest + o_head, (uint32_t)st.ix_head.size(), g_rtpos + o_head, nullptr));
                 // the stream's own view (plan-wise users: k_route, the chunked walks): entry indices are absolute, so the
                 // entries are addressed from the arena's base; positions and nodes are the stream's own
                 DevWalk& dw = h->walks[i];
@@ -332,6 +341,13 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
         h->walks[WC_SLOT] = arena;
     }
     UP(d.walks, h->walks)
+    // k_route's routing tables: a property of the tree, built here once (device_mat.hpp: RouteTables)
+    {
+        const std::vector<RouteTables> blank(1);
+        UP(d.route_tab, blank)
+        HIP_TRY(launch_route_tables(d, const_cast<RouteTables*>(d.route_tab), nullptr));
+        HIP_TRY(hipDeviceSynchronize());
+    }
     // seed signatures (flatmat.hpp): whole-genome samples
     d.seed_sig = nullptr;
     d.seed_stride = d.seed_chunks = d.seed_row_words = 0;

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "flatmat.hpp"
+#include "route_pos.hpp"
 
 namespace wepp {
 
@@ -68,6 +69,21 @@ struct WcInfo {
     SegNode whole;
 };
 
+// k_route's routing tables: what the kernel asks about a stream a read can walk -- the window crowns of every genome
+// window, then the tree-wide streams (wc_info[tw_base + t]) -- as structure of arrays, and its two scans (the first
+// tree-wide stream whose bound covers theta, the first crown of a window whose bound covers the root score) as lookup
+// tables.  All of it is a property of the uploaded tree: one block builds it at upload (launch_route_tables, the one
+// statement of the rule) and every block of k_route copies it into LDS dword by dword.
+constexpr uint32_t RT_MAX = MAX_WINDOWS * WC_MAX + MAX_STREAMS;
+constexpr uint32_t RT_TT_MAX = 64, RT_WT_D = 8;      // theta values / root score - base(root) values the lookup tables reach
+struct RouteTables {
+    int32_t wc_tau[RT_MAX], rt_wbase[RT_MAX];                               // bound; stream-wide aggregate: base
+    uint32_t wc_n[RT_MAX], rt_head[RT_MAX], rt_wbfs[RT_MAX], rt_wcnt[RT_MAX];   // nodes, head_off, aggregate: BFS index, cnt << 1 | hu
+    uint32_t tab_ok;                                                        // 0: a bound the lookup tables do not reach -- k_route scans
+    uint8_t t_tab[RT_TT_MAX], sid_tab[MAX_WINDOWS * RT_WT_D];
+};
+static_assert(sizeof(RouteTables) % 4 == 0, "copied dword by dword");
+
 // tree-wide arrays (global DFS indices)
 struct DevMAT {
     uint32_t N, bm_words, max_pos, n_streams;
@@ -89,6 +105,8 @@ struct DevMAT {
     const DevStream* wc_streams;  // [wc_windows * WC_MAX] their sweep streams (k_sweep_arena)
     uint32_t wc_windows;          // 0: none built
     uint32_t tw_base;             // wc_info[tw_base + t] = tree-wide stream t as a slice of the same arena (what a read that walks it gets as wsid)
+    const RouteTables* route_tab; // k_route's tables of wc_info[0 .. tw_base + n_streams), built at upload
+    const uint32_t* rt_pos;       // [head slots of the arena] events and nesting depth of a position's list in one word (route_pos.hpp)
     uint32_t win_n[MAX_WINDOWS];  // nodes of window w's stream when it is a crown (all the window's candidates, flatmat.hpp), 0xFFFFFFFF when the whole tree
     // seed signatures (flatmat.hpp): nibble (position, chunk of the whole-tree stream); seed_chunks == 0: none built
     const uint32_t* seed_sig;
@@ -299,6 +317,11 @@ hipError_t launch_route(const DevMAT& m, const uint32_t* d_read_off, const uint3
                         uint32_t* job_n, uint8_t* tier_of, int32_t* root_score, uint32_t* blk_counts,
                         uint32_t* tier_info, uint32_t* slot_in_blk, uint32_t* tier_info_next, uint32_t* wsid, const RouteDirect& direct,
                         hipStream_t stream);
+// *out = k_route's tables of `m` (everything but m.route_tab itself must be set); once per uploaded tree
+hipError_t launch_route_tables(const DevMAT& m, RouteTables* out, hipStream_t stream);
+// out[p] = rt_pos_pack(events of list p, nest[p]) for the n_heads head slots of ONE slice of the arena (the last head of
+// a slice only ends the list before it: its word is 0, never its neighbour's)
+hipError_t launch_route_pos(const IxHead* heads, const uint8_t* nest, uint32_t n_heads, uint32_t* out, hipStream_t stream);
 // entry indices of a stream's slice of the walk arena (IxHead::off, IxEnt::up) made absolute: += ent_off
 hipError_t launch_rebase_index(IxHead* heads, uint32_t n_heads, IxEnt* ents, uint32_t n_ents, uint32_t ent_off, hipStream_t stream);
 // the seeded samples of one call: a workgroup per sample writes its final results (seed_kernels.hip)

@@ -7,8 +7,12 @@
 #include "../../include/wepp_place.h"
 #include "errors.hpp"
 #include "flatmat.hpp"
+#include "route_pos.hpp"
 
 extern "C" uint64_t wepp_debug_flatten_count(void) { return wepp::flatten_count(); }
+// (not part of the C-ABI, like wepp_debug_route_stats: bits of the length field of k_route's word per position in THIS
+// build -- tests/route_variant_child.py makes sure it runs the narrowed test build)
+extern "C" uint32_t wepp_debug_route_len_bits(void) { return wepp::RT_LEN_BITS; }
 
 extern "C" int wepp_flat_create(const wepp_tree_desc* tree, wepp_flat_t** out) {
     if (!tree || !out) return wepp::set_error(WEPP_EINVAL, "null argument");

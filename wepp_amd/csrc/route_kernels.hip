@@ -26,6 +26,53 @@ __device__ unsigned long long g_route_stats[16];
 #endif
 
 // -----------------------------------------------------------------------------
+// k_route_tables: k_route's routing tables (device_mat.hpp: RouteTables), one block, once per uploaded tree -- until
+// they moved here every block of every call rebuilt them behind three barriers.
+// -----------------------------------------------------------------------------
+__global__ __launch_bounds__(ROUTE_THREADS) void k_route_tables(DevMAT m, RouteTables* __restrict__ out) {
+    // the routing table of every stream a read can walk -- the window crowns of every genome window, then the tree-wide
+    // streams (wc_info[tw_base + t]): bound, size, where its position index starts in the arena, and its stream-wide
+    // aggregate (what a read without events in it is placed by).  Read from the 80-byte records of the device table,
+    // every one of these was a load of its own in the read's chain of dependent loads.
+    __shared__ RouteTables rt;
+    for (uint32_t i = threadIdx.x; i < sizeof(RouteTables) / 4; i += blockDim.x) ((uint32_t*)&rt)[i] = 0u;
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < m.tw_base + m.n_streams && i < RT_MAX; i += blockDim.x) {
+        const WcInfo q = m.wc_info[i];
+        rt.wc_tau[i] = q.tau; rt.wc_n[i] = q.n; rt.rt_head[i] = q.head_off;
+        rt.rt_wbase[i] = q.whole.base; rt.rt_wbfs[i] = q.whole_bfs; rt.rt_wcnt[i] = (q.whole.cnt << 1) | (q.whole.hu ? 1u : 0u);
+    }
+    // the two scans of a read -- the first tree-wide stream whose bound covers theta, the first crown of its window whose
+    // bound covers its root score -- as table lookups: the bounds are small integers (tree-wide: the flattener's theta
+    // levels; window crowns: base(root) + 0 .. WC_MAX_DTAU, then "any"), so theta and root score - base(root) index
+    // them.  (tab_ok == 0 -- a bound the tables do not reach -- leaves the scans in place.)
+    if (threadIdx.x == 0) rt.tab_ok = (m.n_streams >= 2 && m.tau[m.n_streams - 2] < (int32_t)RT_TT_MAX && m.tau[0] >= 0) ? 1u : 0u;
+    __syncthreads();
+    if (threadIdx.x < RT_TT_MAX) {
+        uint32_t t = m.n_streams - 1;
+        for (uint32_t i = 0; i + 1 < m.n_streams; i++)
+            if ((int32_t)threadIdx.x <= m.tau[i]) { t = i; break; }
+        rt.t_tab[threadIdx.x] = (uint8_t)t;
+    }
+    if (threadIdx.x < m.wc_windows * RT_WT_D && threadIdx.x < MAX_WINDOWS * RT_WT_D) {
+        const uint32_t wi = threadIdx.x / RT_WT_D, d = threadIdx.x % RT_WT_D;
+        // d < RT_WT_D - 1: root score = base(root) + d exactly; d == RT_WT_D - 1: that or more -- only a crown without a
+        // bound serves those, which the table can say as long as every bounded crown's bound is below base(root) + d
+        // (from the LDS copies of the bounds: the barrier above)
+        uint32_t pick = 0xFFu;
+        for (uint32_t i = 0; i < WC_MAX; i++) {
+            const int32_t tau = rt.wc_tau[wi * WC_MAX + i];
+            if (!rt.wc_n[wi * WC_MAX + i]) break;
+            if (tau != 0x7FFFFFFF && (tau < m.root_base || tau >= m.root_base + (int32_t)(RT_WT_D - 1))) atomicAnd(&rt.tab_ok, 0u);
+            if (pick == 0xFFu && m.root_base + (int32_t)d <= tau) pick = i;
+        }
+        rt.sid_tab[threadIdx.x] = (uint8_t)pick;
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < sizeof(RouteTables) / 4; i += blockDim.x) ((uint32_t*)out)[i] = ((const uint32_t*)&rt)[i];
+}
+
+// -----------------------------------------------------------------------------
 // k_route: theta(read) = score(root) + |S| -> index of the smallest stream whose
 // tau covers it.  Per-(block, tier) counts go to blk_counts, per-tier totals and
 // the largest read of each tier to tier_info.
@@ -46,47 +93,14 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
     unsigned long long last_ = __builtin_amdgcn_s_memtime();
 #endif
     __shared__ uint32_t cnt[MAX_PLANS], mx[MAX_PLANS], jobs_of[2 * MAX_STREAMS], open_of[4], events_of[2], resolved_of[1];
-    // the routing table of every stream a read can walk -- the window crowns of every genome window, then the tree-wide
-    // streams (wc_info[tw_base + t]) -- in LDS: bound, size, where its position index starts in the arena, and its
-    // stream-wide aggregate (what a read without events in it is placed by).  Read from the 80-byte records of the
-    // device table, every one of these was a load of its own in the read's chain of dependent loads.
-    constexpr uint32_t RT_MAX = MAX_WINDOWS * WC_MAX + MAX_STREAMS;
-    __shared__ int32_t wc_tau[RT_MAX], rt_wbase[RT_MAX];
-    __shared__ uint32_t wc_n[RT_MAX], rt_head[RT_MAX], rt_nest[RT_MAX], rt_wbfs[RT_MAX], rt_wcnt[RT_MAX];
-    for (uint32_t i = threadIdx.x; i < m.tw_base + m.n_streams && i < RT_MAX; i += blockDim.x) {
-        const WcInfo q = m.wc_info[i];
-        wc_tau[i] = q.tau; wc_n[i] = q.n; rt_head[i] = q.head_off; rt_nest[i] = q.nest_off;
-        rt_wbase[i] = q.whole.base; rt_wbfs[i] = q.whole_bfs; rt_wcnt[i] = (q.whole.cnt << 1) | (q.whole.hu ? 1u : 0u);
-    }
-    // the two scans of a read -- the first tree-wide stream whose bound covers theta, the first crown of its window whose
-    // bound covers its root score -- as table lookups: the bounds are small integers (tree-wide: the flattener's theta
-    // levels; window crowns: base(root) + 0 .. WC_MAX_DTAU, then "any"), so theta and root score - base(root) index
-    // them.  (tab_ok == 0 -- a bound the tables do not reach -- leaves the scans in place.)
-    constexpr uint32_t TT_MAX = 64, WT_D = 8;
-    __shared__ uint8_t t_tab[TT_MAX], sid_tab[MAX_WINDOWS * WT_D];
-    __shared__ uint32_t tab_ok[1];
-    if (threadIdx.x == 0) tab_ok[0] = (m.n_streams >= 2 && m.tau[m.n_streams - 2] < (int32_t)TT_MAX && m.tau[0] >= 0) ? 1u : 0u;
-    __syncthreads();
-    if (threadIdx.x < TT_MAX) {
-        uint32_t t = m.n_streams - 1;
-        for (uint32_t i = 0; i + 1 < m.n_streams; i++)
-            if ((int32_t)threadIdx.x <= m.tau[i]) { t = i; break; }
-        t_tab[threadIdx.x] = (uint8_t)t;
-    }
-    if (threadIdx.x < m.wc_windows * WT_D && threadIdx.x < MAX_WINDOWS * WT_D) {
-        const uint32_t wi = threadIdx.x / WT_D, d = threadIdx.x % WT_D;
-        // d < WT_D - 1: root score = base(root) + d exactly; d == WT_D - 1: that or more -- only a crown without a
-        // bound serves those, which the table can say as long as every bounded crown's bound is below base(root) + d
-        // (from the LDS copies of the bounds: the barrier above)
-        uint32_t pick = 0xFFu;
-        for (uint32_t i = 0; i < WC_MAX; i++) {
-            const int32_t tau = wc_tau[wi * WC_MAX + i];
-            if (!wc_n[wi * WC_MAX + i]) break;
-            if (tau != 0x7FFFFFFF && (tau < m.root_base || tau >= m.root_base + (int32_t)(WT_D - 1))) atomicAnd(&tab_ok[0], 0u);
-            if (pick == 0xFFu && m.root_base + (int32_t)d <= tau) pick = i;
-        }
-        sid_tab[threadIdx.x] = (uint8_t)pick;
-    }
+    // the routing tables of the tree (device_mat.hpp: RouteTables, built at upload) in LDS: one coalesced copy, and one
+    // barrier together with the counters below
+    __shared__ RouteTables rt;
+    for (uint32_t i = threadIdx.x; i < sizeof(RouteTables) / 4; i += blockDim.x) ((uint32_t*)&rt)[i] = ((const uint32_t*)m.route_tab)[i];
+    constexpr uint32_t TT_MAX = RT_TT_MAX, WT_D = RT_WT_D;
+    const auto& wc_tau = rt.wc_tau; const auto& rt_wbase = rt.rt_wbase; const auto& wc_n = rt.wc_n; const auto& rt_head = rt.rt_head;
+    const auto& rt_wbfs = rt.rt_wbfs; const auto& rt_wcnt = rt.rt_wcnt;
+    const auto& t_tab = rt.t_tab; const auto& sid_tab = rt.sid_tab;
     __shared__ uint32_t wl_count[2], wl_base[2], cj_count[2], cl_count[2], cj_base[2], cl_base[2], c_ok[2], ww_count[2], ww_base[2], w16_to_wave[1], ww_cand[2];
     if (threadIdx.x < 2) { cj_count[threadIdx.x] = 0; cl_count[threadIdx.x] = 0; }
     if (threadIdx.x == 0) ww_count[0] = ww_count[1] = ww_cand[0] = ww_cand[1] = 0;
@@ -103,10 +117,11 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
     ROUTE_STAMP(0);      // prologue
     const uint32_t per = (n_reads + gridDim.x - 1) / gridDim.x;
     const uint32_t lo = blockIdx.x * per, hi = min(n_reads, lo + per);
-    const IxHead* __restrict__ ar_head = m.walks[WC_SLOT].ix_head;      // the walk arena: every stream's index is a slice of it
-    const uint8_t* __restrict__ ar_nest = m.walks[WC_SLOT].ix_nest;
+    // a position's events and nesting depth in a stream: one word per head slot of the walk arena (route_pos.hpp); the
+    // arena's list heads themselves are read only where a length field is saturated
+    const uint32_t* __restrict__ ar_pos = m.rt_pos;
     const uint32_t root_w0 = m.node_woff[0], root_w1 = m.node_woff[1];
-    const bool use_tabs = tab_ok[0] != 0;
+    const bool use_tabs = rt.tab_ok != 0;
     // four reads per thread and round: their offsets, then their first two words, are requested together
     // (one read after the other, every read cost its thread three memory round trips in a row)
     const uint32_t lane = threadIdx.x & 63;
@@ -135,7 +150,7 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
       // read by read, every read cost its thread a memory round trip of its own, one after the other
       int c4[4] = {0, 0, 0, 0};
       uint32_t nh4[4] = {0, 0, 0, 0}, t4[4] = {0, 0, 0, 0}, sid4[4] = {NONE, NONE, NONE, NONE}, wi4[4] = {0, 0, 0, 0}, inwin4[4] = {0, 0, 0, 0};
-      uint32_t pre_nest[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, pre_o0[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}}, pre_o1[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+      uint32_t pre_w[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
 #pragma unroll
       for (uint32_t u = 0; u < 4; u++) {
         const uint32_t r = r0 + u * blockDim.x;
@@ -194,11 +209,7 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
 #pragma unroll
                 for (uint32_t j = 0; j < 2; j++) {
                     const uint32_t p = w_pos(fw[u][j]);
-                    if (j < k && p <= m.max_pos) {
-                        pre_nest[u][j] = (uint32_t)ar_nest[rt_nest[tab] + p];
-                        pre_o0[u][j] = ar_head[rt_head[tab] + p].off;
-                        pre_o1[u][j] = ar_head[rt_head[tab] + p + 1].off;
-                    }
+                    if (j < k && p <= m.max_pos) pre_w[u][j] = ar_pos[rt_head[tab] + p];
                 }
             }
         }
@@ -228,17 +239,18 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
         // how a read with at most WALK16_K entries would walk the stream of routing-table entry `tab` (its position index
         // is a slice of the arena): plain, cut into jobs, or not at all (more open intervals than a walk's stack holds)
         auto classify = [&](uint32_t tab, uint32_t& nj_out, uint32_t& open_out, uint32_t& ev_out) -> uint32_t {
-            const IxHead* ix_head = ar_head + rt_head[tab];
-            const uint8_t* ix_nest = ar_nest + rt_nest[tab];
+            const uint32_t* ix_pos = ar_pos + rt_head[tab];
             uint32_t open_max = 0, events = 0, longest = 0;
             for (uint32_t j = 0; j < k; j++) {
                 const uint32_t p = w_pos(j == 0 ? fw[u][0] : j == 1 ? fw[u][1] : read_word[so + j]);
                 if (p <= m.max_pos) {
-                    uint32_t nest, o0, o1;
-                    if (j < 2 && tab == pre_tab) { nest = j ? pre_nest[u][1] : pre_nest[u][0]; o0 = j ? pre_o0[u][1] : pre_o0[u][0]; o1 = j ? pre_o1[u][1] : pre_o1[u][0]; }
-                    else { nest = (uint32_t)ix_nest[p]; o0 = ix_head[p].off; o1 = ix_head[p + 1].off; }
+                    uint32_t nest, len;
+                    if (!rt_pos_unpack(j < 2 && tab == pre_tab ? (j ? pre_w[u][1] : pre_w[u][0]) : ix_pos[p], len, nest)) {
+                        // (a list longer than the field holds: the exact length from its heads; every list ends in a sentinel)
+                        const IxHead* ix_head = m.walks[WC_SLOT].ix_head + rt_head[tab];
+                        len = ix_head[p + 1].off - ix_head[p].off - 1u;
+                    }
                     open_max += nest;
-                    const uint32_t len = o1 - o0 - 1u;      // (every list ends in a sentinel)
                     events += len;
                     longest = max(longest, len);
                 }
@@ -396,37 +408,41 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
       // per wave, ~60 K of them on one address per million reads, made k_route six times slower)
       if (direct.wlist[0]) {
           __syncthreads();
-          if (threadIdx.x < 2) {
-              const uint32_t cc = threadIdx.x;
+          if (threadIdx.x < 64) {
+              // the block's reservations of a round in ONE round trip: lane l of the first wave asks for one range, all of
+              // them in the same instruction (a returning atomic on a word every block adds to is ~3 us, and one thread
+              // used to issue up to three of them one behind the other).  Lane 0: plain walkers of up to 8 entries; 1: those
+              // of 9 - 16, to their own list or to the waves' (below); 2, 3: reads for k_walk_wave of <= 64 / more events;
+              // 4, 5: jobs of the two chunked classes; 6, 7: their reads.
+              const uint32_t l = threadIdx.x, cc = l & 1u;
               // a handful of plain walkers with 9 - 16 entries in the block (a sequencing run: one in a million reads): they
               // join the reads with many events (a wave each, k_walk_wave) -- a launch of their own starts when the walks
-              // of the other class end, ~15 us at the end of every call, for a read or two
-              const bool to_wave = cc == 1 && direct.wwlist && wl_count[1] && wl_count[1] <= WALK16_TO_WAVE_MAX;
-              if (cc == 1) w16_to_wave[0] = to_wave ? 1u : 0u;
-              if (to_wave) {
-                  wl_base[1] = atomicAdd(&tier_info[TI_WWCUR], wl_count[1]);
-                  atomicAdd(&tier_info[TI_W16WAVE], wl_count[1]);
-              } else
-                  wl_base[cc] = wl_count[cc] ? atomicAdd(&tier_info[TI_WCUR + cc], wl_count[cc]) : 0u;
-              wl_count[cc] = 0;
-              // the chunked classes' job tables and lists: the block's ranges, or -- a table outgrown -- the class is
-              // flagged and left to the host's planned launch (the blind kernels leave at once)
-              c_ok[cc] = 0;
-              if (cl_count[cc] && direct.jobs[0]) {
-                  cj_base[cc] = atomicAdd(&tier_info[TI_JCUR + cc], cj_count[cc]);
-                  cl_base[cc] = atomicAdd(&tier_info[TI_CCUR + cc], cl_count[cc]);
-                  if (cj_base[cc] + cj_count[cc] > BLIND_JOB_CAP || cl_base[cc] + cl_count[cc] > BLIND_CHUNKED_READS) tier_info[TI_JOVER + cc] = 1u;
-                  else c_ok[cc] = 1;
+              // of the other class end, ~15 us at the end of every call, for a read or two.  (Decided from the block's
+              // counts in LDS, before any reservation.)
+              const bool to_wave = direct.wwlist && wl_count[1] && wl_count[1] <= WALK16_TO_WAVE_MAX;
+              const bool chunked = l >= 4 && l < 8 && cl_count[cc] && direct.jobs[0];
+              uint32_t n = 0, word = 0;
+              if (l < 2) { n = wl_count[l]; word = (l == 1 && to_wave) ? TI_WWCUR : TI_WCUR + l; }
+              else if (l < 4) { n = min(ww_count[cc], cc ? direct.ww_max_big : direct.ww_max_small); word = TI_WWCUR + cc; }
+              else if (chunked) { n = l < 6 ? cj_count[cc] : cl_count[cc]; word = (l < 6 ? TI_JCUR : TI_CCUR) + cc; }
+              uint32_t base = 0;
+              if (n) base = atomicAdd(&tier_info[word], n);
+              if (l == 1 && to_wave) atomicAdd(&tier_info[TI_W16WAVE], n);
+              const uint32_t peer = (uint32_t)__shfl((int)base, (int)(l ^ 2u));      // (lanes 4, 5: where their class's reads start)
+              if (l < 2) wl_base[l] = base;
+              else if (l < 4) ww_base[cc] = base;
+              else if (l < 6) {
+                  // the chunked classes' job tables and lists: the block's ranges, or -- a table outgrown -- the class is
+                  // flagged and left to the host's planned launch (the blind kernels leave at once)
+                  cj_base[cc] = base;
+                  cl_base[cc] = peer;
+                  const bool over = chunked && (base + n > BLIND_JOB_CAP || peer + cl_count[cc] > BLIND_CHUNKED_READS);
+                  if (over) tier_info[TI_JOVER + cc] = 1u;
+                  c_ok[cc] = chunked && !over ? 1u : 0u;
               }
-              cj_count[cc] = 0;
-              cl_count[cc] = 0;
-              if (cc == 0) {
-                  for (uint32_t b = 0; b < 2; b++) {
-                      const uint32_t n = min(ww_count[b], b ? direct.ww_max_big : direct.ww_max_small);
-                      ww_base[b] = n ? atomicAdd(&tier_info[TI_WWCUR + b], n) : 0u;
-                      ww_count[b] = 0;
-                  }
-              }
+              if (l == 1) w16_to_wave[0] = to_wave ? 1u : 0u;
+              // (the counts were read above by this very wave: cleared for the next round)
+              if (l < 2) { wl_count[l] = 0; ww_count[l] = 0; cj_count[l] = 0; cl_count[l] = 0; }
           }
           __syncthreads();
 #pragma unroll
@@ -483,6 +499,14 @@ __global__ void k_rebase_index(IxHead* __restrict__ heads, uint32_t n_heads, IxE
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_heads) heads[i].off += ent_off;
     if (i < n_ents && ents[i].up != IX_NONE) ents[i].up += ent_off;
+}
+
+// what k_route asks about a position of one stream's slice of the arena, one word per head slot (route_pos.hpp).  Per
+// slice: its last head only ends the last list, and the head behind it belongs to the next stream
+__global__ void k_route_pos(const IxHead* __restrict__ heads, const uint8_t* __restrict__ nest, uint32_t n_heads, uint32_t* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_heads) return;
+    out[i] = i + 1 < n_heads ? rt_pos_pack(heads[i + 1].off - heads[i].off - 1u, nest[i]) : 0u;      // (every list ends in a sentinel)
 }
 
 // -----------------------------------------------------------------------------
@@ -581,10 +605,21 @@ hipError_t launch_route(const DevMAT& m, const uint32_t* d_read_off, const uint3
     return hipGetLastError();
 }
 
+hipError_t launch_route_tables(const DevMAT& m, RouteTables* out, hipStream_t stream) {
+    hipLaunchKernelGGL(k_route_tables, dim3(1), dim3(ROUTE_THREADS), 0, stream, m, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_rebase_index(IxHead* heads, uint32_t n_heads, IxEnt* ents, uint32_t n_ents, uint32_t ent_off, hipStream_t stream) {
     const uint32_t n = std::max(n_heads, n_ents);
     if (!n) return hipSuccess;
     hipLaunchKernelGGL(k_rebase_index, dim3((n + 255) / 256), dim3(256), 0, stream, heads, n_heads, ents, n_ents, ent_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_route_pos(const IxHead* heads, const uint8_t* nest, uint32_t n_heads, uint32_t* out, hipStream_t stream) {
+    if (!n_heads) return hipSuccess;
+    hipLaunchKernelGGL(k_route_pos, dim3((n_heads + 255) / 256), dim3(256), 0, stream, heads, nest, n_heads, out);
     return hipGetLastError();
 }
 
