@@ -32,7 +32,7 @@ void release(wepp_mat* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     for (PlaceLane& L : h->lane) {
         if (L.ws) (void)hipFree(L.ws);
-        if (L.ws2) (void)hipFree(L.ws2);
+        if (L.part) (void)hipFree(L.part);
         if (L.d_info) (void)hipFree(L.d_info);
         if (L.h_info) (void)hipHostFree(L.h_info);
         for (uint32_t i = 0; i < MAX_STREAMS; i++) {
@@ -68,6 +68,26 @@ void release(wepp_mat* h) {
     delete h;
 }
 
+inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// A grow-only buffer of a handle, in device or in pinned host memory: kept while it holds `need` bytes; else freed --
+// behind a device-wide synchronisation: work in flight may still use it, hipFree waits for the device anyway, and a
+// buffer regrows only while its handle warms up -- and allocated again with need / slack bytes to spare.
+int grow_only(void*& p, size_t& have, size_t need, size_t slack, bool pinned, const char* what) {
+    if (need <= have) return WEPP_OK;
+    if (p) {
+        HIP_TRY(hipDeviceSynchronize());
+        (void)(pinned ? hipHostFree(p) : hipFree(p));
+        p = nullptr;
+        have = 0;
+    }
+    const size_t bytes = need + need / slack;
+    const hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string(pinned ? "hipHostMalloc " : "hipMalloc ") + what + ": " + hipGetErrorString(e));
+    have = bytes;
+    return WEPP_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -85,6 +105,8 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     wepp_mat* h = new (std::nothrow) wepp_mat();
     if (!h) return set_error(WEPP_ENOMEM, "out of host memory");
     g_handles_alive.fetch_add(1, std::memory_order_relaxed);
+    // (every error return below releases the handle with what it holds by then; the successful return lets go of it)
+    std::unique_ptr<wepp_mat, void (*)(wepp_mat*)> owner(h, release);
     h->device = device;
     h->bfs2id = f.bfs2id;
     h->dfs2id = f.dfs2id;
@@ -109,8 +131,8 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     h->tun = PlaceTunables::from_env();
     d.walk_eager_nodes = h->tun.walk_eager_nodes;
     int rc;
-#define UP(dst, vec) if ((rc = upload(h, vec, &dst)) != WEPP_OK) { release(h); return rc; }
-    // (inside up_stream a failure returns the code; the caller releases the handle)
+#define UP(dst, vec) if ((rc = upload(h, vec, &dst)) != WEPP_OK) return rc;
+    // (inside up_stream too a failure returns the code: `owner` releases the handle wherever upload_flat returns)
     UP(d.node_woff, f.node_woff) UP(d.words, f.words) UP(d.nstat, f.nstat) UP(d.rank2dfs, f.rank2dfs)
     UP(d.dfs2bfs, f.dfs2bfs) UP(d.rank2bfs, f.rank2bfs)
     {
@@ -192,10 +214,8 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
         for (const Stream& st : f.streams) {
             tot_n += st.n; tot_ent += st.ix_ent.size(); tot_head += st.ix_head.size(); tot_sp += st.sp.size(); tot_dst += st.rq_dst.size();
         }
-        if (tot_ent >= 0xFFFFFFF0ull || tot_n >= 0xFFFFFFF0ull || tot_head >= 0xFFFFFFF0ull || tot_dst >= 0xFFFFFFF0ull) {
-            release(h);
+        if (tot_ent >= 0xFFFFFFF0ull || tot_n >= 0xFFFFFFF0ull || tot_head >= 0xFFFFFFF0ull || tot_dst >= 0xFFFFFFF0ull)
             return set_error(WEPP_ELIMIT, "the walk structures exceed 2^32 index entries");
-        }
         a_head.reserve(wc_head); a_ent.reserve(wc_ent); a_nest.reserve(wc_head); a_sp.reserve(wc_sp);
         a_nrec.reserve(wc_n); a_pre.reserve(wc_n); a_suf.reserve(wc_n); a_dst.reserve(wc_dst);
         for (size_t w = 0; w < f.wcrowns.size(); w++)
@@ -243,7 +263,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
         };
         IxHead* g_head; IxEnt* g_ent; uint8_t *g_nest, *g_sp; NodeRec* g_nrec; SegNode *g_pre, *g_suf, *g_dst;
         uint32_t* g_rtpos;                         // k_route's word per head slot, derived from g_head and g_nest slice by slice (route_pos.hpp)
-#define ARR(ptr, count, front) if ((rc = dev_array(ptr, count, front)) != WEPP_OK) { release(h); return rc; }
+#define ARR(ptr, count, front) if ((rc = dev_array(ptr, count, front)) != WEPP_OK) return rc;
         ARR(g_head, tot_head, a_head) ARR(g_ent, tot_ent, a_ent) ARR(g_nest, tot_head, a_nest) ARR(g_sp, tot_sp, a_sp)
         ARR(g_nrec, tot_n, a_nrec) ARR(g_pre, tot_n, a_pre) ARR(g_suf, tot_n, a_suf) ARR(g_dst, tot_dst, a_dst)
         ARR(g_rtpos, tot_head, std::vector<uint32_t>())
@@ -377,7 +397,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     // (two arrays of WALK_COUNTERS slots: loop iterations of the walks' waves, bytes their lanes asked memory for)
     e = hipMalloc((void**)&h->d_work, wepp_mat::D_WORK_BYTES);
     if (e == hipSuccess) e = hipMemset(h->d_work, 0, wepp_mat::D_WORK_BYTES);
-    if (e != hipSuccess) { release(h); return hip_fail(e, "handle setup"); }
+    if (e != hipSuccess) return hip_fail(e, "handle setup");
     for (PlaceLane& L : h->lane) {
         if (e == hipSuccess) e = hipMalloc((void**)&L.d_info, (2 * TI_WORDS + ROUTE_BLOCKS * MAX_PLANS) * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(L.d_info, 0, 2 * TI_WORDS * sizeof(uint32_t));
@@ -401,8 +421,8 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
             e = hipMalloc(&L.d_seed_heavy, seed_heavy_bytes());
             if (e == hipSuccess) e = hipMemset(L.d_seed_heavy, 0, seed_heavy_bytes());
         }
-    if (e != hipSuccess) { release(h); return hip_fail(e, "handle setup"); }
-    *out = h;
+    if (e != hipSuccess) return hip_fail(e, "handle setup");
+    *out = owner.release();
     return WEPP_OK;
 }
 }  // namespace
@@ -499,8 +519,9 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
 
 // Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes, and
 // even with one host thread their kernels may overlap on the device (each lane has its own compute stream).  Each lane
-// has its own workspace, routing counters, side streams, events and k_seed second-pass table.  What they share on the
-// handle:
+// has its own two device blocks (handle.hpp: the fixed regions, grown before k_route, and the partials, grown once the
+// routing counters are back: a call routes once, whatever its partials need), routing counters, side streams, events
+// and k_seed second-pass table.  What they share on the handle:
 //   - the tree and everything built from it (read-only here);
 //   - the event ring (a slot claimed atomically);
 //   - the hints job_events, ww_by_jobs, step_walkers, expect_jobs8 and expect_lists (atomics; they choose how the next call cuts its work, never its results);
@@ -518,45 +539,18 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     const uint32_t T = mat->tile_reads;
     const uint32_t ns = mat->dev.n_streams;
 
-    // ---- workspace: [tier_of R bytes][list R][root_score R][partials: sum over tiers of nchunks*count*12] ----
-    // The partials are sized for the worst case once the per-tier counts are known.
-    bool ws_moved = false;
-    auto grow = [&](size_t need) -> int {
-        if (need <= L.ws_bytes) return WEPP_OK;
-        // (the plain walks of this call may already run on their side stream, out of the lists in this workspace)
-        if (L.ws) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (uint32_t i : {SIDE_WAVE, SIDE_WALK16, SIDE_PLAN, SIDE_JOBS16, SIDE_JOBS8}) HIP_TRY(hipStreamSynchronize(L.side[i]));
-            (void)hipFree(L.ws);
-            L.ws = nullptr;
-            L.ws_bytes = 0;
-        }
-        // (half as much again: the partials of a batch of long reads vary by a third with the tile size its longest
-        // read allows, and a regrowth costs a hipFree + hipMalloc of ~100 MB -- 16 ms -- plus a second routing pass)
-        need += need / 2;
-        hipError_t e = hipMalloc(&L.ws, need);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc workspace: ") + hipGetErrorString(e));
-        L.ws_bytes = need;
-        ws_moved = true;
-        return WEPP_OK;
-    };
-    const size_t list_bytes = (((size_t)n_reads * 4) + 255) & ~(size_t)255;      // (the plan ids live in mat->d_plan_of)
+    // ---- the lane's two device blocks (handle.hpp: PlaceLane) ----
+    // L.ws, the fixed regions: sized by n_reads alone and grown here, before k_route writes into them, so they stay
+    // where they are for the whole call.  L.part, the partials: sized from the routing counters and grown behind the plan
+    // loop below, before anything of this call has touched it.
+    const size_t list_bytes = pad256((size_t)n_reads * 4);      // (the plan ids live in mat->d_plan_of)
     const PlaceTunables& tun = mat->tun;
     size_t sort_temp = 0;
     HIP_TRY(sort_reads_temp_bytes(n_reads, &sort_temp));
-    sort_temp = (sort_temp + 255) & ~(size_t)255;
-    // fixed part of the workspace: list | root_score | slot in block | jobs | sort keys in/out | sorted lists |
+    sort_temp = pad256(sort_temp);
     // sort temp of the whole-tree plan and of the four walk classes (their sorts run on different side streams)
     constexpr uint32_t N_SORTS = 5;
-    // (+ the chunked walk classes sized blind: first job of a read, and per class its reads, its job table, three partials per job)
-    constexpr size_t blind_bytes = 2 * ((size_t)BLIND_CHUNKED_READS * 4 + (size_t)BLIND_JOB_CAP * 16);
-    const size_t fixed_bytes = 11 * list_bytes + blind_bytes + N_SORTS * sort_temp;      // (8 lists of carve() + key_in, key_out, val_in)
-    {
-        // before routing only the fixed regions are needed; reserve a typical partial size too
-        int rc = grow(fixed_bytes + (size_t)n_reads * 12 * 2);
-        if (rc != WEPP_OK) return rc;
-    }
-    uint8_t* tier_of = nullptr;
+    uint8_t* const tier_of = mat->d_plan_of + plan_base;
     uint32_t *list = nullptr, *slot_in_blk = nullptr, *key_in = nullptr, *key_out = nullptr, *val_in = nullptr;
     uint32_t* job_n = nullptr;       // jobs of every read whose walk is cut into chunks (k_route)
     uint32_t* wlist[2] = {nullptr, nullptr};   // the plain walk classes' reads that have events in their stream (k_route appends them)
@@ -564,36 +558,47 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     uint32_t *b_first = nullptr, *b_clist[2] = {nullptr, nullptr}, *b_jobs[2] = {nullptr, nullptr};   // the chunked classes sized blind (k_route's tables)
     int32_t* b_ps[2] = {nullptr, nullptr};
     uint32_t *b_pr[2] = {nullptr, nullptr}, *b_pc[2] = {nullptr, nullptr};
-    uint32_t* wsid = nullptr;        // the window crown (index into DevMAT::wc_info) of every read routed to slot WC_SLOT
+    uint32_t* const wsid = mat->d_wsid_of + plan_base;   // the window crown (index into DevMAT::wc_info) of every read routed to slot WC_SLOT
     int32_t* root_score = nullptr;
     void* sort_tmp = nullptr;
-    auto carve = [&]() {
-        char* p = (char*)L.ws;
-        tier_of = mat->d_plan_of + plan_base;
-        list = (uint32_t*)p; p += list_bytes;
-        root_score = (int32_t*)p; p += list_bytes;
-        slot_in_blk = (uint32_t*)p; p += list_bytes;
-        job_n = (uint32_t*)p; p += list_bytes;
-        wlist[0] = (uint32_t*)p; p += list_bytes;
-        wlist[1] = (uint32_t*)p; p += list_bytes;
-        b_first = (uint32_t*)p; p += list_bytes;
-        wwlist = (uint32_t*)p; p += list_bytes;
+    // The fixed regions, one cursor over them: run from a null base it gives the block's size, run from L.ws the pointers.
+    auto carve = [&](void* base) -> size_t {
+        size_t off = 0;
+        auto take = [&](auto*& region, size_t bytes) {
+            region = reinterpret_cast<std::remove_reference_t<decltype(region)>>((uintptr_t)base + off);
+            off += bytes;
+        };
+        take(list, list_bytes);
+        take(root_score, list_bytes);
+        take(slot_in_blk, list_bytes);
+        take(job_n, list_bytes);
+        take(wlist[0], list_bytes);
+        take(wlist[1], list_bytes);
+        take(b_first, list_bytes);
+        take(wwlist, list_bytes);
+        // (the chunked walk classes sized blind: per class its reads, its job table, three partials per job)
         for (uint32_t cc = 0; cc < 2; cc++) {
-            b_clist[cc] = (uint32_t*)p; p += (size_t)BLIND_CHUNKED_READS * 4;
-            b_jobs[cc] = (uint32_t*)p; p += (size_t)BLIND_JOB_CAP * 4;
-            b_ps[cc] = (int32_t*)p; p += (size_t)BLIND_JOB_CAP * 4;
-            b_pr[cc] = (uint32_t*)p; p += (size_t)BLIND_JOB_CAP * 4;
-            b_pc[cc] = (uint32_t*)p; p += (size_t)BLIND_JOB_CAP * 4;
+            take(b_clist[cc], (size_t)BLIND_CHUNKED_READS * 4);
+            take(b_jobs[cc], (size_t)BLIND_JOB_CAP * 4);
+            take(b_ps[cc], (size_t)BLIND_JOB_CAP * 4);
+            take(b_pr[cc], (size_t)BLIND_JOB_CAP * 4);
+            take(b_pc[cc], (size_t)BLIND_JOB_CAP * 4);
         }
-        wsid = mat->d_wsid_of + plan_base;
-        key_in = (uint32_t*)p; p += list_bytes;
-        key_out = (uint32_t*)p; p += list_bytes;
-        val_in = (uint32_t*)p; p += list_bytes;   // the sorted lists (same offsets as in `list`)
-        sort_tmp = p;                             // N_SORTS regions of sort_temp bytes
+        take(key_in, list_bytes);
+        take(key_out, list_bytes);
+        take(val_in, list_bytes);                 // the sorted lists (same offsets as in `list`)
+        take(sort_tmp, N_SORTS * sort_temp);
+        return off;
     };
-    carve();
-    uint32_t* tier_info = L.d_info + L.info_idx * TI_WORDS;
-    uint32_t* blk_counts = L.d_info + 2 * TI_WORDS;
+    {
+        // (half as much again, as ever; a device-wide synchronisation in front of the free: the lane's previous call may
+        // still run out of these regions)
+        const int rc = grow_only(L.ws, L.ws_bytes, carve(nullptr), 2, false, "workspace");
+        if (rc != WEPP_OK) return rc;
+    }
+    carve(L.ws);
+    uint32_t* const tier_info = L.d_info + L.info_idx * TI_WORDS;
+    uint32_t* const blk_counts = L.d_info + 2 * TI_WORDS;
 
     // events per job of the two chunked classes: they follow the handle's traffic (device_mat.hpp: WALK_TARGET_JOBS)
     const uint32_t job_events = mat->job_events[0] | (mat->job_events[1] << 16);
@@ -664,10 +669,9 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // (... and then reads of up to 16 events walk plainly, as before the waves: 100 000 reads with 7 - 16 events are
     // nothing to a walk launch -- its time is its longest walk -- and 0.3 ms as jobs)
     const uint32_t walk_limit = (ww_jobs && !tun.ww_fixed) ? std::max(walk_max_events, WALK_MAX_EVENTS_BY_JOBS) : walk_max_events;
-    auto route = [&](bool first) -> int {
+    {
         // the counters alternate between two sets: this call's set is zero (cleared at creation or by the
         // previous k_route), and this k_route clears the other one for the next call
-        tier_info = L.d_info + L.info_idx * TI_WORDS;
         uint32_t* tier_info_next = L.d_info + (L.info_idx ^ 1u) * TI_WORDS;
         // k_route places the reads that have no event in their stream itself and lists the other plain walkers; their
         // walks are launched from those lists at once, sized for the worst case, on a side stream -- the routing
@@ -720,28 +724,16 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
             // below), so their copy goes directly behind the wait, in front of any k_scatter, and an event of its own
             // tells the host when it has landed -- whatever is queued behind it.  The host then returns, and enqueues
-            // the next call's k_route, while k_step still runs.  (A second routing pass after the workspace moved
-            // copies nothing: the counters are the same, and the host has filled TI_OFF into h_info.)
-            if (first) {
-                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-                HIP_TRY(hipEventRecord(L.info_ev, ps));
-            }
-            scattered = false;
-            if (scatter_blind || need_lists) HIP_TRY(scatter());
+            // the next call's k_route, while k_step still runs.
+            HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+            HIP_TRY(hipEventRecord(L.info_ev, ps));
+            if (scatter_blind) HIP_TRY(scatter());
         } else {
             // (no walks: every read is listed, on the caller's stream, the counters behind the lists as ever)
             HIP_TRY(scatter());
-            if (first) {
-                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-                HIP_TRY(hipEventRecord(L.info_ev, ps));
-            }
+            HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+            HIP_TRY(hipEventRecord(L.info_ev, ps));
         }
-        return WEPP_OK;
-    };
-
-    {
-        int rc = route(true);
-        if (rc != WEPP_OK) return rc;
     }
     // the host sizes the launches from the counters, and the GPU idles until it has: poll for them (a
     // blocking wait adds its wake-up, ~15 us per call, to that idle time) ...
@@ -886,7 +878,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
             d.n_list = info[TI_JOBS + cc * MAX_STREAMS + t];
             d.job0 = (uint32_t)n_jobs[cc];
             walkc_off[cc] = info[TI_OFF + plan_id(cls, 0)];
-            d.list = nullptr;
+            d.list = list + walkc_off[cc];
             d.wave_end = (wc.n ? wc.p[wc.n - 1].wave_end : 0u) + walk_plan_waves(d.n_list);
             wc.n++;
             n_jobs[cc] += d.n_list;
@@ -953,22 +945,25 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         p.part_off = part_total;
         part_total += (size_t)p.nchunks * count * 12;
     }
+    if (n_jobs[0] + n_jobs[1] >= (1ull << 31)) return set_error(WEPP_ELIMIT, "too many walk jobs in one call; split the batch");
+    // ---- the lane's second block: the plans' partials and, behind them, what a chunked class the host plans itself
+    // needs -- jobs per read, their scan, the scan's scratch, three partials per job.  Nothing of this call has touched
+    // it; what the lane's previous call left running in it is waited for only when the block has to grow. ----
+    size_t scan_temp[2] = {0, 0}, walkc_base[2] = {0, 0}, part_need = pad256(part_total);
+    for (uint32_t cc = 0; cc < 2; cc++) {
+        if (!walkc[cc].n) continue;
+        HIP_TRY(scan_u32_temp_bytes(walkc_reads[cc], &scan_temp[cc]));
+        walkc_base[cc] = part_need;
+        part_need += 2 * pad256((size_t)walkc_reads[cc] * 4) + pad256(scan_temp[cc]) + 3 * pad256((size_t)n_jobs[cc] * 4);
+    }
     {
-        ws_moved = false;
-        int rc = grow(fixed_bytes + part_total);
+        // (half as much again: the partials of a batch of long reads vary by a third with the tile size its longest
+        // read allows, and a regrowth costs a hipFree + hipMalloc of ~100 MB, 16 ms)
+        const int rc = grow_only(L.part, L.part_bytes, part_need, 2, false, "partials");
         if (rc != WEPP_OK) return rc;
-        if (ws_moved) {
-            // the workspace moved: redo the (cheap) routing into the new buffer
-            carve();
-            rc = route(false);
-            if (rc != WEPP_OK) return rc;
-        }
     }
     if (!scattered && (np || arena_n || seed_n || walkc[0].n || walkc[1].n)) return set_error(WEPP_EDEVICE, "a planned launch without its read list");
-    char* part_base = (char*)L.ws + fixed_bytes;
-    // (the workspace may have moved above: every pointer into it is taken from here on)
-    for (uint32_t cc = 0; cc < 2; cc++)
-        for (uint32_t k = 0; k < walkc[cc].n; k++) walkc[cc].p[k].list = list + walkc_off[cc];
+    char* const part_base = (char*)L.part;
     const bool debug_plans = tun.debug_plans;
     for (uint32_t i = 0; i < np; i++) {
         Plan& p = plans[i];
@@ -1006,7 +1001,6 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     }
     std::sort(order, order + n_plain, [&](uint32_t a, uint32_t b) { return plans[a].bpc > plans[b].bpc; });
     const bool walks = walkc[0].n || walkc[1].n;
-    if (n_jobs[0] + n_jobs[1] >= (1ull << 31)) return set_error(WEPP_ELIMIT, "too many walk jobs in one call; split the batch");
     for (uint32_t cls = 0; cls < 2; cls++)
         passes += (info[TI_WCUR + cls] + 63) / 64;      // a walk "pass" = one wave of 64 reads
     passes += (info[TI_RESOLVED] + 63) / 64 + info[TI_WWCUR] + info[TI_WWCUR + 1];
@@ -1056,29 +1050,15 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (walkc[0].n || walkc[1].n) {
             // chunked walks, per class: jobs per read in list order -> exclusive scan -> the walk (a partial per
             // job; a job finds its read by bisection in the scanned offsets) -> one combination per read.
-            // Buffers: a second grow-only workspace holding both classes.
-            auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-            size_t scan_temp[2] = {0, 0}, need = 0, base[2] = {0, 0};
-            for (uint32_t cc = 0; cc < 2; cc++) {
-                if (!walkc[cc].n) continue;
-                HIP_TRY(scan_u32_temp_bytes(walkc_reads[cc], &scan_temp[cc]));
-                base[cc] = need;
-                need += 2 * pad((size_t)walkc_reads[cc] * 4) + pad(scan_temp[cc]) + 3 * pad((size_t)n_jobs[cc] * 4);
-            }
-            if (need > L.ws2_bytes) {
-                if (L.ws2) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(L.ws2); L.ws2 = nullptr; L.ws2_bytes = 0; }
-                hipError_t e2 = hipMalloc(&L.ws2, need + need / 4);
-                if (e2 != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc walk workspace: ") + hipGetErrorString(e2));
-                L.ws2_bytes = need + need / 4;
-            }
+            // Buffers: each class's share of the lane's second block, behind the plans' partials (walkc_base above).
             for (uint32_t cc = 0; cc < 2; cc++) {
                 if (!walkc[cc].n) continue;
                 // each class on a side stream of its own: a chain of short, latency-bound launches
                 const uint32_t side = cc ? SIDE_JOBS16 : SIDE_JOBS8;
                 HIP_TRY(fork_to(side, q));
                 const uint32_t R3 = walkc_reads[cc], J = (uint32_t)n_jobs[cc];
-                const size_t b_cnt = pad((size_t)R3 * 4), b_tmp = pad(scan_temp[cc]), b_job = pad((size_t)J * 4);
-                char* w2 = (char*)L.ws2 + base[cc];
+                const size_t b_cnt = pad256((size_t)R3 * 4), b_tmp = pad256(scan_temp[cc]), b_job = pad256((size_t)J * 4);
+                char* w2 = part_base + walkc_base[cc];
                 uint32_t* jcnt = (uint32_t*)w2; w2 += b_cnt;
                 uint32_t* joff = (uint32_t*)w2; w2 += b_cnt;
                 void* jtmp = w2; w2 += b_tmp;
@@ -1340,25 +1320,11 @@ extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const
     bool any_staged_out = false;
     for (int i = 0; i < 4; i++) { out_pinned[i] = dst[i] && is_pinned_host(dst[i]); any_staged_out = any_staged_out || (dst[i] && !out_pinned[i]); }
     {
-        auto grow_dev = [&](void*& p, size_t& have, size_t need) -> hipError_t {
-            if (need <= have) return hipSuccess;
-            if (p) { (void)hipDeviceSynchronize(); (void)hipFree(p); p = nullptr; have = 0; }
-            hipError_t r = hipMalloc(&p, need + need / 4);
-            if (r == hipSuccess) have = need + need / 4;
-            return r;
-        };
-        auto grow_pin = [&](void*& p, size_t& have, size_t need) -> hipError_t {
-            if (need <= have) return hipSuccess;
-            if (p) { (void)hipDeviceSynchronize(); (void)hipHostFree(p); p = nullptr; have = 0; }
-            hipError_t r = hipHostMalloc(&p, need + need / 4, hipHostMallocDefault);
-            if (r == hipSuccess) have = need + need / 4;
-            return r;
-        };
-        e = grow_dev(mat->io_in, mat->io_in_bytes, in_need);
-        if (e == hipSuccess) e = grow_dev(mat->io_out, mat->io_out_bytes, out_need);
-        if (e == hipSuccess && !in_pinned) e = grow_pin(mat->pin, mat->pin_bytes, in_need);
-        if (e == hipSuccess && any_staged_out) e = grow_pin(mat->pin_out, mat->pin_out_bytes, out_need);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("device / pinned buffers of the batch: ") + hipGetErrorString(e));
+        int rc = grow_only(mat->io_in, mat->io_in_bytes, in_need, 4, false, "reads of the batch");
+        if (rc == WEPP_OK) rc = grow_only(mat->io_out, mat->io_out_bytes, out_need, 4, false, "results of the batch");
+        if (rc == WEPP_OK && !in_pinned) rc = grow_only(mat->pin, mat->pin_bytes, in_need, 4, true, "reads of the batch");
+        if (rc == WEPP_OK && any_staged_out) rc = grow_only(mat->pin_out, mat->pin_out_bytes, out_need, 4, true, "results of the batch");
+        if (rc != WEPP_OK) return rc;
     }
     uint32_t* const d_off = (uint32_t*)mat->io_in;
     uint32_t* const d_word = (uint32_t*)((char*)mat->io_in + off_bytes);
@@ -1661,22 +1627,9 @@ int check_read_csr(const uint32_t* read_off, const uint32_t* read_word, uint32_t
 // Grow-only buffers of the handle for the pass-2 calls: `dev_bytes` of device memory in io_in and `pin_bytes`
 // of pinned staging (the same buffers wepp_place_batch uses; the calls on a handle are serial).
 int reserve_io(wepp_mat* mat, size_t dev_bytes, size_t pin_need) {
-    if (dev_bytes > mat->io_in_bytes) {
-        if (mat->io_in) { (void)hipFree(mat->io_in); mat->io_in = nullptr; mat->io_in_bytes = 0; }
-        hipError_t e = hipMalloc(&mat->io_in, dev_bytes + dev_bytes / 4);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        mat->io_in_bytes = dev_bytes + dev_bytes / 4;
-    }
-    if (pin_need > mat->pin_bytes) {
-        if (mat->pin) { (void)hipHostFree(mat->pin); mat->pin = nullptr; mat->pin_bytes = 0; }
-        hipError_t e = hipHostMalloc(&mat->pin, pin_need + pin_need / 4, hipHostMallocDefault);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-        mat->pin_bytes = pin_need + pin_need / 4;
-    }
-    return WEPP_OK;
+    const int rc = grow_only(mat->io_in, mat->io_in_bytes, dev_bytes, 4, false, "io buffer");
+    return rc != WEPP_OK ? rc : grow_only(mat->pin, mat->pin_bytes, pin_need, 4, true, "staging buffer");
 }
-
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 

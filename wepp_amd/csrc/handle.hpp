@@ -25,16 +25,21 @@ using namespace wepp;
 // `asked` is not used by the product: the emulation's guard check (tests/cxx/epp_emu.cpp) looks for stores past it.
 struct DevBlock { void* ptr; size_t bytes, asked; };
 
-// What ONE placement call in flight needs of its own: workspace, routing counters, the side streams its launch
+// What ONE placement call in flight needs of its own: two device blocks, routing counters, the side streams its launch
 // chains run on.  A handle has two: the sub-batches of wepp_place_batch alternate between them, so that the routing
 // of sub-batch k+1 (kernels, a device-to-host copy, the host's poll) overlaps the walks of sub-batch k, each lane's
 // work ordered on the lane's own compute stream.  wepp_place_batch_device uses lane 0.
 struct PlaceLane {
-    // grow-only workspace: read list, routing arrays, partial results
+    // Two grow-only blocks, sized at the two moments a call knows the sizes (capi.cpp: place_device).
+    // ws: the regions sized by the number of reads alone -- read list, root scores, routing arrays, walk lists, blind job
+    // tables, sort keys and scratch.  Grown before k_route, which writes into it: it does not move during a call.
     void* ws = nullptr;
     size_t ws_bytes = 0;
-    void* ws2 = nullptr;              // grow-only workspace of the chunked walks (job tables, partials)
-    size_t ws2_bytes = 0;
+    // part: what is sized from the routing counters -- 12 bytes per (chunk, read) of every sweep plan and, behind them,
+    // the job tables and partials of the chunked walks the host plans itself.  Grown behind the plan loop, before
+    // anything of the call has touched it.
+    void* part = nullptr;
+    size_t part_bytes = 0;
     uint32_t* d_info = nullptr;       // two sets of tier_info (TI_WORDS each, used alternately: k_route clears the other one) followed by blk_counts
     uint32_t info_idx = 0;            // the set the next call uses (zero: cleared at creation or by the previous call's k_route)
     uint32_t* h_info = nullptr;       // pinned copy of tier_info
