@@ -19,6 +19,7 @@
 
 #include "handle.hpp"
 #include "host_pool.hpp"
+#include "info_wait.hpp"
 
 namespace {
 
@@ -401,7 +402,12 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     for (PlaceLane& L : h->lane) {
         if (e == hipSuccess) e = hipMalloc((void**)&L.d_info, (2 * TI_WORDS + ROUTE_BLOCKS * MAX_PLANS) * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemset(L.d_info, 0, 2 * TI_WORDS * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_info, TI_WORDS * sizeof(uint32_t), hipHostMallocDefault);
+        // (the report block of k_step, handle.hpp: the device stores into it, the host polls its last line)
+        if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_info, info_block_words(TI_WORDS) * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped);
+        if (e == hipSuccess) {
+            memset(L.h_info, 0, info_block_words(TI_WORDS) * sizeof(uint32_t));
+            e = hipHostGetDevicePointer((void**)&L.d_report, L.h_info, 0);
+        }
         for (uint32_t i = 0; i < MAX_STREAMS && e == hipSuccess; i++) {
             e = hipStreamCreateWithFlags(&L.side[i], hipStreamNonBlocking);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&L.join_ev[i], hipEventDisableTiming);
@@ -620,6 +626,18 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // what the side streams of a call wait for: the event behind k_route.  The timing event of the call's ring slot is
     // recorded there anyway and serves (a second record cost a call into the runtime per step).
     const hipEvent_t fork_from = step_unfused ? L.route_ev : mat->ev0[ev_slot];
+    // THE COUNTERS' WAY TO THE HOST.  A call with k_step has the kernel report them: its first wave copies them into the
+    // lane's block of host memory and stores this call's sequence number behind them (walk_kernels.hip), the host polls
+    // that word -- no second stream, no copy, no event in front of the poll.  Every other call (walks off,
+    // WEPP_STEP_UNFUSED=1) and WEPP_INFO_COPY=1 (A/B aid and fallback) copy them on the plan stream and poll an event.
+    const bool report = walking && !step_unfused && !tun.info_copy && n_reads > 0;
+    uint32_t report_seq = 0;
+    if (report) report_seq = L.info_seq = info_next_seq(L.info_seq);
+    // THE TWO TIME STAMPS ride on the kernels' own dispatch packets: ev0 is the stop event of k_route's launch, ev1 the
+    // one of k_step's -- re-recorded at the end of the call when something was joined into the caller's stream behind
+    // k_step.  WEPP_STAMP_RECORDS=1 (A/B aid): two records of their own, as before.  The span means the same either way.
+    const bool ext_stamps = !tun.stamp_records;
+    bool ev1_on_step = false;
     // the 8-entry job class (reads with more events than a wave pass takes): launched blind behind k_route only when the
     // handle's previous call held such reads -- two launches that find nothing, a fork and a join otherwise --, else from
     // the counters like the 16-entry class.  A hint: a call it misleads launches the class late and places every read.
@@ -639,6 +657,11 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     bool scattered = false;           // k_scatter of this call is queued on ps
     auto scatter = [&]() -> hipError_t {
         scattered = true;
+        // (a call by report has put nothing on the plan stream yet: it forks here, in front of its first launch there)
+        if (report) {
+            const hipError_t e = hipStreamWaitEvent(ps, fork_from, 0);
+            if (e != hipSuccess) return e;
+        }
         return launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps);
     };
     // one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
@@ -681,9 +704,9 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                                           d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, walk_max_events,
                                           tun.ww_fixed ? tun.ww_block_max_small : ww_jobs ? 0u : 0xFFFFFFFFu, tun.ww_fixed ? tun.ww_block_max_big : ww_jobs ? 0u : 0xFFFFFFFFu};
         HIP_TRY(launch_route(mat->dev, d_read_off, d_read_word, n_reads, mat->use_crowns, walking ? walk_limit : 0u, job_events, WALK8_ROWS, WALK16_ROWS, seed_min_hard, tun.seed_min_nodes, job_n, tier_of, root_score, blk_counts,
-                             tier_info, slot_in_blk, tier_info_next, wsid, direct, stream));
+                             tier_info, slot_in_blk, tier_info_next, wsid, direct, stream, ext_stamps ? mat->ev0[ev_slot] : nullptr));
         L.info_idx ^= 1u;
-        HIP_TRY(hipEventRecord(mat->ev0[ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
+        if (!ext_stamps) HIP_TRY(hipEventRecord(mat->ev0[ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
         if (walking) {
             if (step_unfused) HIP_TRY(hipEventRecord(L.route_ev, stream));
             // Launched BLIND, sized for the worst case, before the routing counters are back: the plain walkers of at most
@@ -716,17 +739,23 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                 const uint32_t group = (!tun.step_groups || !few || walk_limit > 16u) ? 0u : walk_limit > 8u ? 16u : 8u;
                 if (tun.debug_plans) fprintf(stderr, "[step] walkers by groups of %u lanes (0: lane = read); plain walkers of the previous call: %u\n", group, mat->step_walkers.load(std::memory_order_relaxed));
                 HIP_TRY(launch_step(mat->dev, group, WALK8_ROWS, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
-                                    d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream));
+                                    d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream,
+                                    report ? StepReport{tier_info, L.d_report, report_seq} : StepReport{nullptr, nullptr, 0u}, ext_stamps ? mat->ev1[ev_slot] : nullptr));
+                ev1_on_step = ext_stamps && n_reads > 0;      // (no reads, no launch)
             }
             // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
             if (jobs8_blind) HIP_TRY(blind_side(PLAN_WALKC8, SIDE_JOBS8));
-            HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
             // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
-            // below), so their copy goes directly behind the wait, in front of any k_scatter, and an event of its own
-            // tells the host when it has landed -- whatever is queued behind it.  The host then returns, and enqueues
-            // the next call's k_route, while k_step still runs.
-            HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-            HIP_TRY(hipEventRecord(L.info_ev, ps));
+            // below -- a blind k_scatter may write those words while k_step reports them).  By report, k_step has them
+            // on their way as its first act and the plan stream stays empty unless k_scatter goes blind (it forks
+            // itself).  By copy, the copy goes directly behind the plan stream's wait, in front of any k_scatter, and an
+            // event of its own tells the host when it has landed -- whatever is queued behind it.  Either way the host
+            // then returns, and enqueues the next call's k_route, while k_step still runs.
+            if (!report) {
+                HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
+                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
+                HIP_TRY(hipEventRecord(L.info_ev, ps));
+            }
             if (scatter_blind) HIP_TRY(scatter());
         } else {
             // (no walks: every read is listed, on the caller's stream, the counters behind the lists as ever)
@@ -737,7 +766,23 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     }
     // the host sizes the launches from the counters, and the GPU idles until it has: poll for them (a
     // blocking wait adds its wake-up, ~15 us per call, to that idle time) ...
-    {
+    if (report) {
+        // ... the sequence word of the report block (info_wait.hpp: spinning, then yielding, and from 2 ms on asking the
+        // caller's stream now and then, so that a call whose report cannot come ends with an error instead of waiting on)
+        volatile const uint32_t* const word = L.h_info + info_seq_word(TI_WORDS);
+        const hipEvent_t step_ev = ev1_on_step ? mat->ev1[ev_slot] : nullptr;
+        const auto t_poll = std::chrono::steady_clock::now();
+        const InfoWaitResult w = wait_info_word(
+            report_seq, [&]() { return __atomic_load_n(word, __ATOMIC_ACQUIRE); },
+            [&]() {
+                const hipError_t q = step_ev ? hipEventQuery(step_ev) : hipStreamQuery(stream);
+                (void)hipGetLastError();
+                return q == hipSuccess ? 0 : q == hipErrorNotReady ? -1 : (int)q;
+            },
+            [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_poll).count(); });
+        if (w.what == InfoWait::stream_error) return hip_fail((hipError_t)w.error, "waiting for the routing counters");
+        if (w.what == InfoWait::lost) return set_error(WEPP_EDEVICE, "internal error: k_step ended without reporting the routing counters of its call");
+    } else {
         // ... spinning for the first 200 us (the routing kernel of a million reads takes ~45, behind the reads' H2D), then yielding the core
         // between queries -- eight ranks spinning on the cores of one container starve their own staging workers --,
         // and after ~2 ms (a long queue in front of this call) waiting blocking
@@ -761,6 +806,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         L.h_info[TI_OFF + MAX_PLANS] = off;
     }
     const uint32_t* info = L.h_info;
+    if (tun.debug_plans) fprintf(stderr, "[info] counters by %s, lane %u, sequence %u\n", report ? "report" : "copy", lane_idx, report_seq);
     if (tun.debug_plans)
         fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
                 n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
@@ -791,10 +837,10 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         }
     }
     // Hazards of a call WITHOUT k_scatter (scattered == false from here on): nothing of this call reads blk_counts,
-    // tier_of's slots or slot_in_blk -- per lane, rewritten by the lane's next k_route -- and nothing runs on ps behind
-    // the copy the host has seen complete, so ps needs no join.  k_step reads TI_WCUR / TI_WWCUR of this call's counter
-    // set on the caller's stream, in front of the next k_route, which clears the OTHER set; the set after that clears
-    // this one, behind everything this call put on the caller's stream.  A k_scatter that was launched, blind or late,
+    // tier_of's slots or slot_in_blk -- per lane, rewritten by the lane's next k_route -- and nothing runs on ps -- by
+    // report nothing was put there, by copy the host has seen the copy complete --, so ps needs no join.  k_step reads
+    // this call's counter set (its two cursors; all of it for the report) on the caller's stream, in front of the next
+    // k_route, which clears the OTHER set; the set after that clears this one, behind everything this call put on the caller's stream.  A k_scatter that was launched, blind or late,
     // reads those per-lane buffers and writes TI_OFF into this call's set: it and every consumer behind it are joined
     // into the caller's stream below, before the call returns.
     if (tun.debug_plans) fprintf(stderr, "[lists] scatter=%s plan stream joined=%d\n", scatter_mode, (int)(walking && scattered));
@@ -1179,6 +1225,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
                                       ps));
     }
     for (uint32_t i = 0; i < n_joins; i++) HIP_TRY(hipStreamWaitEvent(ps, L.join_ev[joins[i]], 0));
+    bool joined = false;              // something was joined into the caller's stream behind k_step
     if (walking) {
         // the plan stream, when something ran on it behind the counters' copy (k_scatter and what reads its lists: no
         // consumer is launched without it), and the blind walks' side streams join the caller's stream
@@ -1190,8 +1237,11 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS8], 0));
         if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_WALK16], 0));
         if (late16[1]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS16], 0));
+        joined = scattered || step_unfused || jobs8_blind || late8 || late16[0] || late16[1];
     }
-    HIP_TRY(hipEventRecord(mat->ev1[ev_slot], stream));
+    // (the end of the timed span: k_step's own stop event when the kernel is the call's last work on the caller's
+    // stream, else a record behind the joins -- which takes the event over from the launch)
+    if (!ev1_on_step || joined) HIP_TRY(hipEventRecord(mat->ev1[ev_slot], stream));
     {
         std::lock_guard<std::mutex> lk(mat->stat_mu);
         mat->last_passes = passes;

@@ -236,10 +236,15 @@ constexpr uint32_t STEP_GROUPS_MAX_WALKERS = 75000;
 // WALK8_K entries as launch_walk_blind places them, and -- wwlist != nullptr -- the reads with many events as
 // launch_walk_wave places them (wwcount = its two cursors), in the first workgroups.  group = 8 / 16: the walkers by
 // groups of that many lanes a read (place_dev.hpp: group_read; no walker of the call holds more events than that);
-// 0: lane = read
+// 0: lane = read.  report != nullptr: the first wave of the grid's first workgroup copies the TI_WORDS counters at
+// tier_info (final: k_route has ended) to report[0 .. TI_WORDS) -- host memory the device can store into -- and then
+// stores `seq` to report[info_seq_word(TI_WORDS)] with a system-scope release, before it takes its role (info_wait.hpp).
+// stop: as launch_route's.
+struct StepReport { const uint32_t* tier_info; uint32_t* report; uint32_t seq; };
 hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
                        const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
+                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream,
+                       const StepReport& rep = StepReport{nullptr, nullptr, 0u}, hipEvent_t stop = nullptr);
 // a chunked class sized blind: jobs[0 .. *n_jobs) (k_route's table), partials into jb.part_*, then the combination over
 // clist[0 .. *n_class); both leave at once when *jb.skip != 0
 hipError_t launch_walk_jobs_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, const WalkJobs& jb, const uint32_t* jobs, const uint32_t* n_jobs,
@@ -316,7 +321,7 @@ hipError_t launch_route(const DevMAT& m, const uint32_t* d_read_off, const uint3
                         uint32_t seed_min_hard, uint32_t seed_min_nodes,
                         uint32_t* job_n, uint8_t* tier_of, int32_t* root_score, uint32_t* blk_counts,
                         uint32_t* tier_info, uint32_t* slot_in_blk, uint32_t* tier_info_next, uint32_t* wsid, const RouteDirect& direct,
-                        hipStream_t stream);
+                        hipStream_t stream, hipEvent_t stop = nullptr);     // (stop: an event bound to the kernel's own dispatch, complete and stamped when the kernel ends)
 // *out = k_route's tables of `m` (everything but m.route_tab itself must be set); once per uploaded tree
 hipError_t launch_route_tables(const DevMAT& m, RouteTables* out, hipStream_t stream);
 // out[p] = rt_pos_pack(events of list p, nest[p]) for the n_heads head slots of ONE slice of the arena (the last head of

@@ -42,7 +42,12 @@ struct PlaceLane {
     size_t part_bytes = 0;
     uint32_t* d_info = nullptr;       // two sets of tier_info (TI_WORDS each, used alternately: k_route clears the other one) followed by blk_counts
     uint32_t info_idx = 0;            // the set the next call uses (zero: cleared at creation or by the previous call's k_route)
-    uint32_t* h_info = nullptr;       // pinned copy of tier_info
+    // the host's copy of tier_info AND the report block of k_step (info_wait.hpp: info_block_words): coherent, mapped
+    // host memory -- TI_WORDS counters and, on a cache line of its own, the sequence word of the call that wrote them.
+    // A call without a report fills the counters by a copy on the plan stream and leaves the sequence word alone.
+    uint32_t* h_info = nullptr;
+    uint32_t* d_report = nullptr;     // the same block as the device addresses it
+    uint32_t info_seq = 0;            // sequence number of the lane's last call that asked for a report (never 0 once one has)
     // the launch chains of a call are independent: they run concurrently on side streams
     hipStream_t side[MAX_STREAMS] = {};
     hipEvent_t fork_ev = nullptr, join_ev[MAX_STREAMS] = {};

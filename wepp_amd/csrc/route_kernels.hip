@@ -5,6 +5,7 @@
 // the root's score, so a read with theta = score(root) + |S| only needs the "crown" of nodes with base <= theta
 // (plus ancestors); a read confined to a genome window needs the window crown its ROOT score admits.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include <algorithm>
@@ -598,10 +599,13 @@ hipError_t launch_route(const DevMAT& m, const uint32_t* d_read_off, const uint3
                         int use_crowns, uint32_t walk_max_events, uint32_t job_events, uint32_t stack8, uint32_t stack16,
                         uint32_t seed_min_hard, uint32_t seed_min_nodes, uint32_t* job_n, uint8_t* tier_of,
                         int32_t* root_score, uint32_t* blk_counts, uint32_t* tier_info, uint32_t* slot_in_blk,
-                        uint32_t* tier_info_next, uint32_t* wsid, const RouteDirect& direct, hipStream_t stream) {
-    hipLaunchKernelGGL(k_route, dim3(ROUTE_BLOCKS), dim3(ROUTE_THREADS), 0, stream, m, d_read_off, d_read_word,
-                       n_reads, use_crowns, walk_max_events, job_events, std::min(stack8, WALK8_STACK), std::min(stack16, WALK16_STACK),
-                       seed_min_hard, seed_min_nodes, job_n, tier_of, root_score, blk_counts, tier_info, slot_in_blk, tier_info_next, wsid, direct);
+                        uint32_t* tier_info_next, uint32_t* wsid, const RouteDirect& direct, hipStream_t stream, hipEvent_t stop) {
+#define WEPP_ROUTE_ARGS m, d_read_off, d_read_word, n_reads, use_crowns, walk_max_events, job_events, std::min(stack8, WALK8_STACK), std::min(stack16, WALK16_STACK), \
+                        seed_min_hard, seed_min_nodes, job_n, tier_of, root_score, blk_counts, tier_info, slot_in_blk, tier_info_next, wsid, direct
+    // (a stop event rides on the kernel's own dispatch packet: no packet of its own behind the kernel)
+    if (stop) hipExtLaunchKernelGGL(k_route, dim3(ROUTE_BLOCKS), dim3(ROUTE_THREADS), 0, stream, nullptr, stop, 0, WEPP_ROUTE_ARGS);
+    else hipLaunchKernelGGL(k_route, dim3(ROUTE_BLOCKS), dim3(ROUTE_THREADS), 0, stream, WEPP_ROUTE_ARGS);
+#undef WEPP_ROUTE_ARGS
     return hipGetLastError();
 }
 

@@ -24,8 +24,10 @@ struct PlaceTunables {
     bool step_unfused = false;           // WEPP_STEP_UNFUSED=1: plain walks, k_walk_wave and the 8-entry job class as three blind launches behind k_route instead of k_step (the form before it; results identical)
     bool step_groups = true;             // WEPP_STEP_GROUPS=0: the plain walkers of k_step lane = read (walk_body) instead of by lane groups (place_dev.hpp: group_read; results identical)
     bool scatter_blind = false;          // WEPP_SCATTER_BLIND=1: k_scatter launched blind behind the counters' copy in every call, whether or not a launch reads its lists (the form before the lists became lazy; results identical)
+    bool info_copy = false;              // WEPP_INFO_COPY=1: the routing counters reach the host by a copy on the plan stream and an event in every call, instead of k_step's report (the form before the report, and the one every call without k_step keeps; results identical)
+    bool stamp_records = false;          // WEPP_STAMP_RECORDS=1: the two time stamps of a call as event records of their own, instead of stop events of k_route's and k_step's launches (the form before; results and the span's meaning identical)
     // seeds: whole-genome samples
-    bool seed = true;                    // WEPP_SEED=0: whole-genome samples take the tile sweeps
+    bool seed = true;                   // WEPP_SEED=0: whole-genome samples take the tile sweeps
     bool seed_heavy = true;              // WEPP_SEED_HEAVY=0: no second pass (a sample's workgroup evaluates every chunk it must itself)
     uint32_t seed_min_hard = SEED_MIN_HARD;          // WEPP_SEED_MIN_HARD
     uint32_t seed_min_nodes = SEED_MIN_STREAM_NODES; // WEPP_SEED_MIN_NODES
@@ -47,6 +49,8 @@ struct PlaceTunables {
         t.step_unfused = env::is_set("WEPP_STEP_UNFUSED") && env::flag("WEPP_STEP_UNFUSED", false);
         t.step_groups = env::flag("WEPP_STEP_GROUPS", true);
         t.scatter_blind = env::is_set("WEPP_SCATTER_BLIND") && env::flag("WEPP_SCATTER_BLIND", false);
+        t.info_copy = env::is_set("WEPP_INFO_COPY") && env::flag("WEPP_INFO_COPY", false);
+        t.stamp_records = env::is_set("WEPP_STAMP_RECORDS") && env::flag("WEPP_STAMP_RECORDS", false);
         t.seed = env::flag("WEPP_SEED", true);
         t.seed_heavy = env::flag("WEPP_SEED_HEAVY", true);
         t.seed_min_hard = (uint32_t)env::u64("WEPP_SEED_MIN_HARD", SEED_MIN_HARD, 0, 0xFFFFu);

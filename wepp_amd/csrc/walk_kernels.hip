@@ -1,11 +1,13 @@
 // walk_kernels.hip -- the per-read walk: a read visits only the events of the positions IT lists, through the
 // stream's position index, with range queries over the static scores in between.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 
 #include <algorithm>
 
 #include "device_mat.hpp"
+#include "info_wait.hpp"
 #include "place_dev.hpp"
 
 namespace wepp {
@@ -586,7 +588,37 @@ __global__ __launch_bounds__(64 * WALK_WAVES) __attribute__((amdgpu_waves_per_eu
                                               uint32_t* __restrict__ flags, unsigned long long* __restrict__ work_counter,
                                               const uint32_t* __restrict__ wsid, const uint32_t* __restrict__ wlist,
                                               const uint32_t* __restrict__ wcount, const uint32_t* __restrict__ wwlist,
-                                              const uint32_t* __restrict__ wwcount) {
+                                              const uint32_t* __restrict__ wwcount, const uint32_t* __restrict__ tier_info,
+                                              uint32_t* __restrict__ report, uint32_t report_seq) {
+    // THE REPORT: the routing counters to the host, by the first wave of the first workgroup and no other, before it
+    // takes its role -- the workgroup is dispatched first, so this is the first thing the launch issues.  The counters
+    // are final (k_route has ended, by stream order: plain loads); the block is host memory, so the stores leave the
+    // chip; the sequence word goes out behind them (system-scope fence, the wave's own wait, system-scope release) and
+    // tells the host's poll whose counters these are.  Nothing waits for anything here and nobody on the device reads
+    // the block.
+    // THE FORM OF THE LAST TWO STEPS IS THE COMPILER'S PRICE.  An atomic STORE, and a volatile asm, each count as a write
+    // to all memory in the rest of the kernel: every uniform load behind them (the index heads, the window records)
+    // turns from a scalar into a vector load, and the walkers spilled 24 - 68 bytes a lane to scratch.  A fence does
+    // not count, nor does an atomic EXCHANGE on a pointer nothing else aliases (`report` is restrict), nor an asm
+    // without side effects -- so the flag goes out as an exchange whose result nobody reads (no return, same packet on
+    // the bus as a store), and the wait is tied to the value the exchange writes, which keeps it in front of it.
+    // Registers, SGPR spills and scratch of the three instantiations are then the ones without the report (77 / 80 /
+    // 75 VGPRs, no scratch).  The machine code reads: stores, buffer_wbl2 sc0 sc1, s_waitcnt vmcnt(0) lgkmcnt(0), the
+    // wave's s_waitcnt vmcnt(0), global_atomic_swap sc1.  Check it again when the compiler changes.
+    if (report && blockIdx.x == 0 && __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0) {
+        // (unrolled: the loads of all rounds are in flight together)
+        constexpr uint32_t ROUNDS = (TI_WORDS + 63) / 64;
+        uint32_t w[ROUNDS];
+#pragma unroll
+        for (uint32_t k = 0; k < ROUNDS; k++) w[k] = (k * 64 + threadIdx.x < TI_WORDS) ? tier_info[k * 64 + threadIdx.x] : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k < ROUNDS; k++)
+            if (k * 64 + threadIdx.x < TI_WORDS) report[k * 64 + threadIdx.x] = w[k];
+        __threadfence_system();
+        uint32_t seq = report_seq;
+        asm("s_waitcnt vmcnt(0)" : "+v"(seq));
+        if (threadIdx.x == 0) (void)__hip_atomic_exchange(report + info_seq_word(TI_WORDS), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     uint32_t* lds_all;
     if constexpr (G != 0) {
         __shared__ __attribute__((aligned(16))) uint32_t lds_wave[ww_lds_words(WALK_WAVES)];
@@ -726,7 +758,8 @@ hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows,
 
 hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
                        const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
+                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream,
+                       const StepReport& rep, hipEvent_t stop) {
     static_assert(STEP_WAVE_WGS % WALK_XCDS == 0 && WALK_PLAN_ALIGN % (WALK_XCDS * WALK_WAVES) == 0,
                   "the workgroups behind the wave-role ones keep their XCD order, and their number is a multiple of the XCDs");
     if (max_reads == 0) return hipSuccess;
@@ -735,14 +768,23 @@ hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uin
     const uint32_t sd = walk_stack_rows(stack_rows, WALK8_STACK);
     // (the grid is the one of lane = read whatever the form: with groups its workgroups loop when the list needs more)
     const dim3 grid(wave_cap + walk_plan_waves(max_reads) / WALK_WAVES), block(64 * WALK_WAVES);
-#define WEPP_STEP_ARGS m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, wlist, wcount, wwlist, wwcount
-    if (group == 8) hipLaunchKernelGGL(k_step<8>, grid, block, 0, stream, WEPP_STEP_ARGS);
-    else if (group == 16) hipLaunchKernelGGL(k_step<16>, grid, block, 0, stream, WEPP_STEP_ARGS);
+    if (rep.report && !rep.tier_info) return hipErrorInvalidValue;
+#define WEPP_STEP_ARGS m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, wlist, wcount, wwlist, wwcount, \
+                       rep.tier_info, rep.report, rep.seq
+    // (a stop event rides on the kernel's own dispatch packet, as in launch_route)
+#define WEPP_STEP_LAUNCH(G, lds)                                                                                  \
+    do {                                                                                                          \
+        if (stop) hipExtLaunchKernelGGL(k_step<G>, grid, block, lds, stream, nullptr, stop, 0, WEPP_STEP_ARGS);   \
+        else hipLaunchKernelGGL(k_step<G>, grid, block, lds, stream, WEPP_STEP_ARGS);                             \
+    } while (0)
+    if (group == 8) WEPP_STEP_LAUNCH(8, 0);
+    else if (group == 16) WEPP_STEP_LAUNCH(16, 0);
     else {
         // (with the default stack rows the walkers' request is the larger one)
         const uint32_t lds = std::max(walk_lds_bytes(WALK8_K, sd), wave_cap ? ww_lds_words(WALK_WAVES) * 4u : 0u);
-        hipLaunchKernelGGL(k_step<0>, grid, block, lds, stream, WEPP_STEP_ARGS);
+        WEPP_STEP_LAUNCH(0, lds);
     }
+#undef WEPP_STEP_LAUNCH
 #undef WEPP_STEP_ARGS
     return hipGetLastError();
 }
