@@ -8,8 +8,8 @@
  * the reference) needs seconds per read at 16 M nodes; this one needs ~0.1 s and is what the
  * full-size GPU tests compare against.  It is trusted only as far as tests/test_incremental.py
  * shows it equal to o_place_sample (scores of EVERY node, eligibility, winner, counts, the list of
- * optimal nodes) on >= 10 000 random (tree, sample) pairs.  PARITY UNPINNED, like the rest of
- * oracle/ (see mapper2_oracle.c).
+ * optimal nodes) on >= 10 000 random (tree, sample) pairs, and as far as tests/test_reference_pin.py
+ * shows it equal to the reference's own compiled scorer on small trees.
  *
  * What it restates (file:line relative to /root/reference/src), in closed form (SURVEY.md
  * Appendix A.1-A.5):

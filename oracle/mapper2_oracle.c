@@ -5,15 +5,16 @@
  * this file; only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
  * leg use it, and only as the checker / reported CPU baseline.
  *
- * PARITY UNPINNED: the reference (TurakhiaLab/WEPP) ships no tests, golden
- * vectors or fixtures for this path, and its sources
- * cannot be compiled in this image without writing stand-ins for TBB, Boost
- * and protobuf headers (usher_graph.hpp:10 includes <tbb/queuing_rw_mutex.h>,
- * mutation_annotated_tree.hpp pulls tbb + boost + parsimony.pb.h), which the
- * build rules forbid.  The only reference-derived known answer available is
- * the 7-node smoke result recorded in SURVEY.md Appendix B (checked by
- * tests/test_oracle.py).  Everything else in this file is a line-by-line
- * restatement of the cited reference code.
+ * PARITY: the reference (TurakhiaLab/WEPP) ships no tests, golden vectors or
+ * fixtures for this path.  This file is a
+ * line-by-line restatement of the cited reference code, and it is held to the
+ * reference's own compiled scorer: tests/ref_bridge.py builds the reference's
+ * usher_mapper.cpp and tree routines behind oracle/ref_driver.cpp and the
+ * stand-in headers of oracle/ref_shim/, tests/golden/ref_*.json record what
+ * that binary computed, and tests/test_reference_pin.py compares every field
+ * (and 20 000 fresh fuzz pairs where the reference's sources are present).
+ * Trees beyond a few hundred nodes rest on this restatement alone
+ * (DESIGN.md section 6).
  *
  * What is restated (file:line relative to /root/reference/src):
  *   o_mapper2_body()      usher_mapper.cpp:168-506  (mapper2_body; the excess / imputed
@@ -769,6 +770,87 @@ int oracle_excess_at_node(const otree *T, int nS, const int32_t *s_pos, const ui
     }
     free(scratch.v); free(scratch.pos); free(imp); free(exc); free(nhu); free(st.best_j_vec.v); free(S);
     return n_exc;
+}
+
+/* Both lists of one (sample, node) pair with all four fields of each MAT::Mutation, as the -p mode leaves them
+ * in node_excess_mutations[j] / node_imputed_mutations[j] (usher_common.cpp:393-394, :409).  exc / imp need room
+ * for nS + (mutations on the root path) and nS entries; the counts go to n_out[0] (excess) and n_out[1]. */
+static void lists_at_node(const otree *T, const omut *S, int nS, uint32_t j, omut *exc, omut *imp, int *n_out,
+                          anc_vec *scratch, uint8_t *nhu) {
+    o_best_state st;
+    np_state_init(&st, T, nS, nhu);
+    st.best_set_difference = 0x3fffffff;
+    int dummy_sd = 0;
+    o_mapper2_input inp;
+    fill_input(&inp, T, &st, S, nS, j, NULL);
+    inp.set_difference = &dummy_sd;
+    inp.imputed_mutations = imp;
+    inp.n_imputed = &n_out[1];
+    inp.excess_mutations = exc;
+    inp.n_excess = &n_out[0];
+    n_out[0] = n_out[1] = 0;
+    o_mapper2_body(&inp, 1, scratch);
+    free(st.best_j_vec.v);
+}
+
+static size_t tree_mutations(const otree *T) {
+    size_t m = 0;
+    for (int i = 0; i < T->n; i++) m += (size_t)T->nodes[i].nmuts;
+    return m;
+}
+
+int oracle_lists_at_node(const otree *T, int nS, const int32_t *s_pos, const uint8_t *s_ref, const uint8_t *s_mut,
+                         const uint8_t *s_missing, uint32_t j, int32_t *exc4, int32_t *imp4, int32_t *n_out) {
+    omut *S = (omut *)calloc((size_t)(nS ? nS : 1), sizeof(omut));
+    for (int i = 0; i < nS; i++) {
+        S[i].position = s_pos[i]; S[i].ref_nuc = (int8_t)s_ref[i]; S[i].par_nuc = (int8_t)s_ref[i];
+        S[i].mut_nuc = (int8_t)s_mut[i]; S[i].is_missing = s_missing[i];
+    }
+    size_t cap = (size_t)nS + tree_mutations(T) + 1;
+    omut *exc = (omut *)calloc(cap, sizeof(omut)), *imp = (omut *)calloc((size_t)nS + 1, sizeof(omut));
+    uint8_t *nhu = (uint8_t *)calloc((size_t)T->n, 1);
+    anc_vec scratch = {0, 0, 0, 0};
+    int n[2];
+    lists_at_node(T, S, nS, j, exc, imp, n, &scratch, nhu);
+    for (int i = 0; i < n[0]; i++) {
+        exc4[4 * i] = exc[i].position; exc4[4 * i + 1] = exc[i].ref_nuc; exc4[4 * i + 2] = exc[i].par_nuc; exc4[4 * i + 3] = exc[i].mut_nuc;
+    }
+    for (int i = 0; i < n[1]; i++) {
+        imp4[4 * i] = imp[i].position; imp4[4 * i + 1] = imp[i].ref_nuc; imp4[4 * i + 2] = imp[i].par_nuc; imp4[4 * i + 3] = imp[i].mut_nuc;
+    }
+    n_out[0] = n[0]; n_out[1] = n[1];
+    free(scratch.v); free(scratch.pos); free(nhu); free(exc); free(imp); free(S);
+    return 0;
+}
+
+/* FNV-1a over 32-bit words of, per node in BFS order: the excess list (its length, then position, ref_nuc, par_nuc,
+ * mut_nuc of every entry) and the imputed list likewise.  oracle/ref_driver.cpp computes the same number from the
+ * reference's own vectors, so that a fuzz run compares every list of every node without moving them. */
+int oracle_lists_digest(const otree *T, int nS, const int32_t *s_pos, const uint8_t *s_ref, const uint8_t *s_mut,
+                        const uint8_t *s_missing, uint64_t *out) {
+    omut *S = (omut *)calloc((size_t)(nS ? nS : 1), sizeof(omut));
+    for (int i = 0; i < nS; i++) {
+        S[i].position = s_pos[i]; S[i].ref_nuc = (int8_t)s_ref[i]; S[i].par_nuc = (int8_t)s_ref[i];
+        S[i].mut_nuc = (int8_t)s_mut[i]; S[i].is_missing = s_missing[i];
+    }
+    size_t cap = (size_t)nS + tree_mutations(T) + 1;
+    omut *exc = (omut *)calloc(cap, sizeof(omut)), *imp = (omut *)calloc((size_t)nS + 1, sizeof(omut));
+    uint8_t *nhu = (uint8_t *)calloc((size_t)T->n, 1);
+    anc_vec scratch = {0, 0, 0, 0};
+    uint64_t h = 1469598103934665603ull;
+#define DG(w) (h = (h ^ (uint64_t)(uint32_t)(int32_t)(w)) * 1099511628211ull)
+    for (int j = 0; j < T->n; j++) {
+        int n[2];
+        lists_at_node(T, S, nS, (uint32_t)j, exc, imp, n, &scratch, nhu);
+        DG(n[0]);
+        for (int i = 0; i < n[0]; i++) { DG(exc[i].position); DG(exc[i].ref_nuc); DG(exc[i].par_nuc); DG(exc[i].mut_nuc); }
+        DG(n[1]);
+        for (int i = 0; i < n[1]; i++) { DG(imp[i].position); DG(imp[i].ref_nuc); DG(imp[i].par_nuc); DG(imp[i].mut_nuc); }
+    }
+#undef DG
+    *out = h;
+    free(scratch.v); free(scratch.pos); free(nhu); free(exc); free(imp); free(S);
+    return 0;
 }
 
 /* ======================================================================== *

@@ -1,12 +1,14 @@
 """Generates tests/golden/mapper2_cases.json.
 
-The reference has no tests or fixtures for this path and cannot
-be built in this image without stand-in headers, so these vectors are produced
-by oracle/mapper2_oracle.c (the line-by-line C restatement of mapper2_body and
-the usher_common per-sample loop).  They pin the oracle against regressions
-and give the GPU path fixed inputs; they are NOT reference-generated.  The one
-reference-derived known answer is the SURVEY.md Appendix B case, stored under
-"survey_appendix_b" with the values printed in SURVEY.md.
+The reference has no tests or fixtures for this path.  These
+vectors are produced by oracle/mapper2_oracle.c (the line-by-line C restatement
+of mapper2_body and the usher_common per-sample loop): they pin the oracle
+against regressions and give the GPU path fixed inputs, and they are NOT
+reference-generated.  The reference-made fixtures are the ref_*.json files next
+to this one: make_ref_golden.py writes them with oracle/_ref/ref_driver, the
+reference's own usher_mapper.cpp and tree routines compiled behind the stand-in
+headers of oracle/ref_shim/ (tests/ref_bridge.py), over these hand cases and
+fresh fuzz trees; tests/test_reference_pin.py holds this file's oracle to them.
 
 Run from the repo root:  python tests/golden/make_golden.py
 """
@@ -46,13 +48,14 @@ def run_case(name, tree, samples, note=""):
     return dict(name=name, note=note, tree=tree_to_json(tree), bfs_ids=[int(x) for x in ot.bfs_ids()], results=outs)
 
 
-def hand_cases():
+def hand_case_inputs():
+    """[(name, tree, samples, note)]: the hand-made inputs, shared with make_ref_golden.py"""
     cases = []
     # ((A,B),(C,D)) from SURVEY.md Appendix B
     t = Tree.from_lists([-1, 0, 0, 1, 1, 2, 2],
                         [[], [(100, A, A, G)], [(400, T, T, C)], [(200, C, C, T)], [(300, G, G, A)], [(100, A, A, G)], []])
-    cases.append(run_case("survey_appendix_b", t, [[(100, A, G, 0), (200, C, T, 0), (500, A, C, 0)]],
-                          "expected -p scores 3,2,4,1,3,3,5; best leaf A (bfs j=3), score 1, num_best 1"))
+    cases.append(("survey_appendix_b", t, [[(100, A, G, 0), (200, C, T, 0), (500, A, C, 0)]],
+                  "expected -p scores 3,2,4,1,3,3,5; best leaf A (bfs j=3), score 1, num_best 1"))
     samples = [
         [],                                                    # empty S
         [(100, A, N, 1), (200, C, N, 1)],                      # all-N
@@ -63,7 +66,7 @@ def hand_cases():
         [(100, A, C, 0)],                                      # other allele at a mutated site
         [(150, C, T, 0)],                                      # site the tree never mutates
     ]
-    cases.append(run_case("quartet_edge_samples", t, samples))
+    cases.append(("quartet_edge_samples", t, samples, ""))
     # root with mutations (one masked), back-mutation on a branch, repeated position, zero-mutation internal node
     t2 = Tree.from_lists(
         [-1, 0, 0, 1, 1, 2, 2, 3, 3],
@@ -79,15 +82,19 @@ def hand_cases():
     s2 = [[], [(10, A, C, 0)], [(10, A, G, 0), (30, T, C, 0)], [(20, G, T, 0)], [(20, G, N, 1)],
           [(10, A, G, 0), (20, G, T, 0), (30, T, C, 0), (40, C, G, 0)], [(40, C, A, 0)], [(50, A, T, 0)],
           [(10, A, C | G, 0), (60, T, A, 0)]]
-    cases.append(run_case("root_muts_masked_backmut", t2, s2))
+    cases.append(("root_muts_masked_backmut", t2, s2, ""))
     # ties: equal scores broken by num_leaves then by larger bfs j
     t3 = Tree.from_lists([-1, 0, 0, 0, 1, 1, 2, 2, 3],
                          [[], [(5, A, A, C)], [(5, A, A, C)], [(5, A, A, C)], [], [], [], [], []])
-    cases.append(run_case("ties_num_leaves_then_bfs", t3, [[(5, A, C, 0)], [(5, A, C, 0), (9, G, T, 0)], []]))
+    cases.append(("ties_num_leaves_then_bfs", t3, [[(5, A, C, 0)], [(5, A, C, 0), (9, G, T, 0)], []], ""))
     # single node
     t4 = Tree.from_lists([-1], [[(7, C, C, T)]])
-    cases.append(run_case("single_node", t4, [[], [(7, C, T, 0)], [(7, C, G, 0)], [(8, A, G, 0)]]))
+    cases.append(("single_node", t4, [[], [(7, C, T, 0)], [(7, C, G, 0)], [(8, A, G, 0)]], ""))
     return cases
+
+
+def hand_cases():
+    return [run_case(name, tree, samples, note) for (name, tree, samples, note) in hand_case_inputs()]
 
 
 def main():

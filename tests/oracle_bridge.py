@@ -49,6 +49,9 @@ def lib():
             ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
         L.oracle_excess_at_node.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [
             ctypes.c_uint32, ctypes.c_int] + [ctypes.c_void_p] * 4
+        L.oracle_lists_at_node.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + [
+            ctypes.c_uint32] + [ctypes.c_void_p] * 3
+        L.oracle_lists_digest.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 5
         L.oracle_mapper_body.argtypes = [ctypes.c_void_p, ctypes.c_uint8, ctypes.c_int] + [ctypes.c_void_p] * 5
         L.oracle_place_batch_nodepar.argtypes = [ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 6 + [ctypes.c_int]
         L.oracle_epp_map.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32] + [ctypes.c_void_p] * 12 + [
@@ -151,6 +154,29 @@ class OracleTree:
         c = lib().oracle_excess_at_node(self._h, n, _p(pos if n else z32), _p(ref if n else z8), _p(mut if n else z8),
                                         _p(missing if n else z8), int(bfs_j), capacity, _p(op), _p(orf), _p(opa), _p(om))
         return list(zip(op[:c].tolist(), orf[:c].tolist(), opa[:c].tolist(), om[:c].tolist()))
+
+    def lists_at_node(self, pos, ref, mut, missing, bfs_j):
+        """(excess, imputed) of the -p mode at one node, every entry [position, ref, par, mut]."""
+        pos = np.ascontiguousarray(pos, np.int32); ref = np.ascontiguousarray(ref, np.uint8)
+        mut = np.ascontiguousarray(mut, np.uint8); missing = np.ascontiguousarray(missing, np.uint8)
+        n = len(pos)
+        exc = np.zeros((n + int(self._keep[1][-1]) + 1, 4), np.int32); imp = np.zeros((n + 1, 4), np.int32)
+        cnt = np.zeros(2, np.int32)
+        z32 = np.zeros(1, np.int32); z8 = np.zeros(1, np.uint8)
+        lib().oracle_lists_at_node(self._h, n, _p(pos if n else z32), _p(ref if n else z8), _p(mut if n else z8),
+                                   _p(missing if n else z8), int(bfs_j), _p(exc), _p(imp), _p(cnt))
+        return exc[: cnt[0]].tolist(), imp[: cnt[1]].tolist()
+
+    def lists_digest(self, pos, ref, mut, missing):
+        """The digest oracle/ref_driver.cpp writes as "lists": every node's excess and imputed list of the -p mode."""
+        pos = np.ascontiguousarray(pos, np.int32); ref = np.ascontiguousarray(ref, np.uint8)
+        mut = np.ascontiguousarray(mut, np.uint8); missing = np.ascontiguousarray(missing, np.uint8)
+        n = len(pos)
+        out = np.zeros(1, np.uint64)
+        z32 = np.zeros(1, np.int32); z8 = np.zeros(1, np.uint8)
+        lib().oracle_lists_digest(self._h, n, _p(pos if n else z32), _p(ref if n else z8), _p(mut if n else z8),
+                                  _p(missing if n else z8), _p(out))
+        return int(out[0])
 
     def mapper_body(self, ref_nuc, var_node, var_nuc):
         """One VCF row through the Fitch-Sankoff mapper_body: list of (node id, par_nuc, mut_nuc)."""

@@ -41,6 +41,117 @@ def test_golden_fixtures_through_the_c_abi():
         mat.close()
 
 
+def _fixture_mat(case):
+    import ref_cases as rc
+    samples = rc.samples_of(case)
+    mat = w.Mat(rc.tree_of(case))
+    assert mat.bfs_order().tolist() == case["bfs_ids"], case["name"]
+    return mat, samples, Reads.from_lists(samples)
+
+
+def test_reference_fixtures_placement_through_the_c_abi():
+    """tests/golden/ref_mapper2_*.json and ref_digest_*.json: what the REFERENCE's compiled mapper2_body recorded
+    (tests/golden/make_ref_golden.py), not the oracle.  place_batch in both modes, best_nodes, and the imputed
+    mutations of the chosen node; trees of 1 .. 173 nodes, 4 to 9 samples each."""
+    import ref_cases as rc
+    cases = rc.load("ref_mapper2") + rc.load("ref_digest")
+    n_reads = n_best = n_imputed = 0
+    for case in cases:
+        mat, samples, reads = _fixture_mat(case)
+        for mode, per_node in (("place", False), ("p", True)):
+            res = mat.place_batch(reads, per_node_scores=per_node)
+            want = {k: np.array([r["asc"][mode][k] for r in case["results"]]) for k in ("score", "num_best", "best_j", "has_unique")}
+            assert_same(res, want, (case["name"], mode))
+            if per_node:
+                assert res.per_node_scores.tolist() == [r["asc"]["p"]["node_scores"] for r in case["results"]], case["name"]
+        res = mat.place_batch(reads)
+        got = mat.best_nodes(reads, res)
+        imp = mat.imputed_mutations(reads, res.best_bfs_j)
+        for q, r in enumerate(case["results"]):
+            assert got[q].tolist() == r["asc"]["place"]["best_j_vec"], (case["name"], q)
+            assert imp[q] == [tuple(e) for e in r["asc"]["place"]["imputed_best"]], (case["name"], q)
+            n_best += len(got[q])
+            n_imputed += len(imp[q])
+        n_reads += reads.n_reads
+        mat.close()
+    assert n_reads >= 70 and n_best > n_reads and n_imputed > 10, (n_reads, n_best, n_imputed)
+
+
+def test_reference_fixtures_excess_mutations_through_the_c_abi():
+    """node_excess_mutations of EVERY (sample, node) pair of ref_mapper2_*.json and ref_digest_*.json against what
+    the reference recorded: same mutations, same order, masked nodes and masked root mutations included in the trees.
+    Where the fixture holds the lists they are compared entry by entry; every sample's lists are compared through the
+    recorded digest over all nodes (ref_cases.excess_digest, held to the oracle's lists on the CPU).
+
+    The one documented difference (include/wepp_place.h): a masked ROOT mutation that carries nucleotides with
+    ref_nuc != mut_nuc is listed by the reference at the root with its position < 0, first among the back-mutations
+    (it enters the root's ancestral set, usher_mapper.cpp:267-270, which :290 sorts by position, and is appended at
+    :429-443); wepp_excess_mutations does not list it, because a tree read from a .pb never holds one (the loader
+    zeroes those nucleotides, mutation_annotated_tree.cpp:583-588).  The score of the root counts it on both sides (the
+    test above).  So: equal lists everywhere, and at the root the reference's list without its entries of position
+    < 0 -- which tests/test_reference_pin.py shows to be that one entry and nothing else."""
+    import ref_cases as rc
+    n_lists = n_muts = n_dropped = n_entrywise = 0
+    for case in rc.load("ref_mapper2") + rc.load("ref_digest"):
+        mat, samples, reads = _fixture_mat(case)
+        n = len(case["bfs_ids"])
+        pr = np.repeat(np.arange(len(samples), dtype=np.uint32), n)
+        pj = np.tile(np.arange(n, dtype=np.uint32), len(samples))
+        got = mat.excess_mutations(reads, pr, pj)
+        nonzero_masked_root = rc.root_masked_kinds(case)[1]
+        for q, r in enumerate(case["results"]):
+            mine = got[q * n:(q + 1) * n]
+            if case["lists"]:
+                for j in range(n):
+                    ref_list = [tuple(e) for e in r["asc"]["p"]["excess"][j]]
+                    want = [e for e in ref_list if e[0] >= 0]
+                    if len(want) != len(ref_list):
+                        assert nonzero_masked_root and j == 0 and len(ref_list) == len(want) + 1, (case["name"], q, j)
+                    assert mine[j] == want, (case["name"], q, j)
+                    n_entrywise += 1
+            assert rc.excess_digest(mine) == r["asc"]["p"]["excess_listed"], (case["name"], q)
+            assert r["asc"]["p"]["excess_masked"] == 0 or nonzero_masked_root
+            n_dropped += r["asc"]["p"]["excess_masked"]
+            n_lists += n
+            n_muts += sum(len(e) for e in mine)
+        mat.close()
+    assert n_lists > 1500 and n_muts > 5000 and n_entrywise > 250 and n_dropped > 0, (n_lists, n_muts, n_entrywise, n_dropped)
+
+
+def test_reference_fixtures_clades_through_the_c_abi():
+    """set_clades / clade_assign on the annotated fixtures (ref_clades_*.json): best clade and the sorted clade list
+    per column as the reference's own Tree::get_clade_assignment and the loop of usher_common.cpp:603-615 recorded
+    them; the hub tree has segments of 1, 2, 64 and 65 optimal nodes."""
+    import ref_cases as rc
+    from clades_model import expected_arrays
+    cases = rc.load("ref_clades_hub") + rc.load("ref_clades_fuzz")
+    cur_key, cur = None, None
+    seg = set()
+    for case in cases:
+        key = case.get("same_tree_as", case["name"])       # a further annotation of the tree before it: same handle
+        if key != cur_key:
+            if cur:
+                cur[0].close()
+            cur_key, cur = key, _fixture_mat(case)
+        mat, samples, reads = cur
+        columns = case["columns"]
+        cid, und, names = w.number_clade_names(columns)
+        name_ids = [{nm: i + 1 for i, nm in enumerate(col)} for col in names]
+        per_sample = [[(best, lst) for (best, lst) in r["asc"]["place"]["clades"]] for r in case["results"]]
+        want = expected_arrays(per_sample, name_ids)
+        mat.set_clades(cid, und)
+        res = mat.place_batch(reads)
+        off, nodes = mat.best_nodes_csr(reads, res)
+        assert [int(x) for x in res.best_bfs_j] == [r["asc"]["place"]["best_j"] for r in case["results"]], case["name"]
+        assert [int(x) for x in nodes] == [j for r in case["results"] for j in r["asc"]["place"]["best_j_vec"]], case["name"]
+        got = mat.clade_assign(reads, res, off, nodes)
+        for a, b, what in zip(got, want, ("best_clade", "hist_off", "hist_clade", "hist_count")):
+            assert np.array_equal(a, b), (case["name"], what)
+        seg |= set(r["asc"]["place"]["num_best"] for r in case["results"])
+    cur[0].close()
+    assert {1, 2, 64, 65} <= seg
+
+
 @pytest.mark.parametrize("tile", [1, 5, 64])
 def test_fuzz_trees_vs_oracle(oracle, tile):
     rng = np.random.default_rng(100 + tile)
@@ -918,7 +1029,8 @@ def test_excess_mutations_vs_oracle(oracle):
     rng = np.random.default_rng(606)
     n_lists = n_muts = 0
     for it in range(25):
-        # masked root mutations with non-zero nucleotides are the documented exception
+        # masked root mutations with non-zero nucleotides are the documented exception: the reference lists such a
+        # mutation at the root, test_reference_fixtures_excess_mutations_through_the_c_abi holds the library to the rest
         tree, ref = ft.random_tree(rng, p_root_masked=0.0)
         samples = [ft.random_sample(rng, ref) for _ in range(6)]
         reads = ft.reads_from_samples(samples)

@@ -1,8 +1,8 @@
 """CPU tests of oracle/mapper2_oracle.c (the restatement of the reference).
 
-Parity is UNPINNED by the reference itself (no tests/fixtures upstream, and the
-reference cannot be built here); the only reference-derived known answer is the
-SURVEY.md Appendix B smoke result checked first.
+The reference ships no tests or fixtures for this path; the SURVEY.md Appendix B
+smoke result is checked first.  What holds this oracle to the reference's own
+compiled scorer is tests/test_reference_pin.py.
 """
 import json
 import os
