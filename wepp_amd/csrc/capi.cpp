@@ -889,7 +889,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // the tile rule.  Reads per tile: at most MAX_TILE_ENTRIES read words per tile (long reads share a sweep between
     // fewer reads), a power of two, never more than the knob; long reads take the dense (table) variant of the sweep
     auto tile_reads = [&](uint32_t maxk) { uint32_t Tp = T; while (Tp > 1 && (uint64_t)Tp * maxk > MAX_TILE_ENTRIES) Tp >>= 1; return Tp; };
-    auto takes_table = [&](uint32_t maxk) { return maxk <= MAX_TILE_ENTRIES && maxk >= DENSE_MIN_READ_WORDS && mat->dev.max_pos <= DENSE_MAX_POS; };
+    auto takes_table = [&](uint32_t maxk) { return maxk <= MAX_TILE_ENTRIES && maxk >= DENSE_MIN_READ_WORDS && mat->dev.max_pos < DENSE_MAX_POS; };
     uint64_t win_tiles = 0;
     if (fuse_windows)
         for (uint32_t id = 0; id < MAX_PLANS; id++) {

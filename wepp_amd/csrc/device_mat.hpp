@@ -395,7 +395,9 @@ inline uint32_t sweep_lds_bytes(uint32_t bm_words, uint32_t ent_cap, uint32_t ke
            (dense ? key_cap * 4 + DENSE_WAVES_PER_WG * 3 * 64 * 4 + DENSE_WINDOW * 2 : 0);
 }
 // read words per tile: the plain variant is bounded by its LDS request, the dense variant by
-// the 13-bit entry index of its sorted keys (pos:19 | idx:13, hence also max_pos < 2^19)
+// the 13-bit entry index of its sorted keys (pos:19 | idx:13).  Position field DENSE_MAX_POS is reserved for "matches
+// no event": it is what the padding keys (0xFFFFFFFF) carry and what a read position at or beyond it is stored as
+// (read positions reach 2^20 - 2), so the variant takes only trees with max_pos < DENSE_MAX_POS
 constexpr uint32_t MAX_TILE_ENTRIES = 8192;
 constexpr uint32_t DENSE_MAX_POS = (1u << 19) - 1;
 constexpr uint32_t DENSE_MIN_READ_WORDS = 16; // tiles of reads this long keep the sorted position index

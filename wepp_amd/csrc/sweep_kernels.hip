@@ -271,7 +271,8 @@ __device__ __forceinline__ void sweep_tile(
             const uint32_t p = w_pos(w);
             if (S_IN_LDS) S_lds[lds_off + j] = w;
             if (DENSE) {
-                skey[lds_off + j] = (p << 13) | (lds_off + j);
+                // (position field DENSE_MAX_POS = matches no event: read positions beyond it, and the padding keys)
+                skey[lds_off + j] = (min(p, DENSE_MAX_POS) << 13) | (lds_off + j);
                 owner[lds_off + j] = (uint8_t)lane;
             }
             if (p <= max_pos) atomicOr(&bitmap[(p >> 5) & bm_mask], 1u << (p & 31));
