@@ -1053,3 +1053,42 @@ def test_excess_mutations_vs_oracle(oracle):
                 n_muts += len(want)
         mat.close()
     assert n_lists > 3000 and n_muts > 5000
+
+
+@pytest.mark.gpu
+def test_excess_mutations_regrown_block_and_reused_block(oracle):
+    """wepp_excess_mutations launches twice -- count, then emit -- and sizes the output between the two: when the
+    handle's device block has to grow for the list it moves, and the inputs are staged and sent up again behind the
+    new base (pass2_capi.cpp: stage_inputs, called at both places).  A fresh handle and every (read, node) pair of 16
+    reads on a tree of 300 nodes take that path; the same call again finds a block that holds everything and does not.
+
+    The sizes, every region padded to 256 bytes: offsets 17 x 4 -> 256, words (at most 16 x 20) x 4 -> at most 1 280,
+    pair reads, pair nodes and counts 4 800 x 4 = 19 200 each, output offsets 4 800 x 8 = 38 400: the fixed part is
+    at most 97 536 bytes, and the block a fresh handle allocates for the counting launch a quarter more, at most
+    121 920.  The emit launch needs the fixed part and 4 bytes per listed mutation: it outgrows the block from about
+    6 100 mutations, 1.3 per pair, and these pairs list some three times the fixed part (asserted below: more than twice).  The wrapper
+    asks twice per call, first with no capacity to learn the size -- that call returns behind the counting launch --
+    so it is the second C call that regrows the block, and neither C call of the second round does."""
+    rng = np.random.default_rng(607)
+    tree, ref = ft.random_tree(rng, n_nodes=300, max_muts=8, p_root_masked=0.0)     # (masked root mutations: test_excess_mutations_vs_oracle)
+    samples = [ft.random_sample(rng, ref, max_k=20) for _ in range(16)]
+    reads = ft.reads_from_samples(samples)
+    ot = oracle.OracleTree(tree)
+    n = tree.n_nodes
+    pr = np.repeat(np.arange(len(samples), dtype=np.uint32), n)
+    pj = np.tile(np.arange(n, dtype=np.uint32), len(samples))
+    want = []
+    for S in samples:
+        cols = list(zip(*S)) if S else ([], [], [], [])
+        want += [ot.excess_at_node(*cols, j) for j in range(n)]
+    pad = lambda b: (b + 255) & ~255
+    fixed = pad(4 * (len(samples) + 1)) + pad(max(4 * reads.read_word.size, 16)) + 3 * pad(4 * len(pr)) + pad(8 * len(pr))
+    listed = pad(4 * sum(len(x) for x in want))
+    assert listed > 2 * fixed and fixed + listed > fixed + fixed // 4
+    mat = w.Mat(tree)
+    first = mat.excess_mutations(reads, pr, pj)
+    second = mat.excess_mutations(reads, pr, pj)
+    mat.close()
+    assert first == want
+    assert second == want
+    assert first == second

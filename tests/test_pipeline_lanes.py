@@ -1,4 +1,4 @@
-"""wepp_place_batch's pipeline (capi.cpp): a host batch of 65 536 reads or more is cut into S sub-batches, sub-batch k
+"""wepp_place_batch's pipeline (place_batch.cpp): a host batch of 65 536 reads or more is cut into S sub-batches, sub-batch k
 placed on the handle's lane k % 2, from one host thread or from two.  Every plan class goes through both lanes here --
 whole-genome samples far from the tree among them, which k_seed hands to its second pass through a table of the lane
 (seed_kernels.hip: SeedHeavy) -- and every result must be the unsplit call's.
@@ -40,7 +40,7 @@ def new_mat(tree, **env):
 
 
 def sub_ranges(n, S):
-    """the reads [lo, hi) of the S sub-batches of a call of n reads (capi.cpp: sub_lo)"""
+    """the reads [lo, hi) of the S sub-batches of a call of n reads (read_check.hpp: sub_lo)"""
     return [(n * k // S, n * (k + 1) // S) for k in range(S)]
 
 

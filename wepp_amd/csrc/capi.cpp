@@ -7,7 +7,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <functional>
 #include <cstdio>
 #include <cstdlib>
 #include <chrono>
@@ -18,7 +17,6 @@
 #include <vector>
 
 #include "handle.hpp"
-#include "host_pool.hpp"
 #include "info_wait.hpp"
 
 namespace {
@@ -69,7 +67,13 @@ void release(wepp_mat* h) {
     delete h;
 }
 
-inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+namespace wepp {
+
+uint32_t handles_alive() { return g_handles_alive.load(std::memory_order_relaxed); }
+
+size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // A grow-only buffer of a handle, in device or in pinned host memory: kept while it holds `need` bytes; else freed --
 // behind a device-wide synchronisation: work in flight may still use it, hipFree waits for the device anyway, and a
@@ -89,7 +93,7 @@ int grow_only(void*& p, size_t& have, size_t need, size_t slack, bool pinned, co
     return WEPP_OK;
 }
 
-}  // namespace
+}  // namespace wepp
 
 namespace {
 // the device half of wepp_mat_create: the flat image `f` (flatmat.hpp) copied into HBM of `device`, plus the handle's
@@ -506,7 +510,7 @@ extern "C" int wepp_mat_set_use_walk(wepp_mat_t* mat, int enable) {
     return WEPP_OK;
 }
 
-namespace {
+namespace wepp {
 // The placement of one batch whose reads are on the device.  plan_base / plan_total: the batch is reads
 // [plan_base, plan_base + n_reads) of a call of plan_total reads (a sub-batch of wepp_place_batch's pipeline; a
 // direct wepp_place_batch_device call is the whole: base 0, total n_reads) -- where its plan ids go in d_plan_of.
@@ -535,7 +539,7 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
 //   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
 int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
                  uint32_t* d_best_bfs_j, int32_t* d_score, uint32_t* d_num_best, uint32_t* d_flags, hipStream_t stream,
-                 uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx = 0) {
+                 uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx) {
     PlaceLane& L = mat->lane[lane_idx];
     {
         // (a pipelined wepp_place_batch has sized them for the whole call before its sub-batches start, on one thread)
@@ -1259,7 +1263,7 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     }
     return WEPP_OK;
 }
-}  // namespace
+}  // namespace wepp
 
 extern "C" int wepp_place_batch_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word,
                                        uint32_t n_reads, uint64_t n_read_words, uint32_t* d_best_bfs_j,
@@ -1310,605 +1314,6 @@ extern "C" int wepp_mat_last_timing(wepp_mat_t* mat, float* mean_sweep_ms, uint3
     if (n_calls) *n_calls = n;
     if (passes) *passes = mat->acc_passes / std::max<uint64_t>(1, mat->n_timed);
     if (algorithmic_bytes) *algorithmic_bytes = (mat->acc_bytes + wb) / std::max<uint64_t>(1, mat->n_timed);
-    return WEPP_OK;
-}
-
-namespace {
-// pinned (hipHostMalloc / hipHostRegister) host memory can be the source or the target of a DMA as it stands
-bool is_pinned_host(const void* p) {
-    if (!p) return false;
-    hipPointerAttribute_t a{};
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-}  // namespace
-
-// Host buffers in, host buffers out.  A large batch runs as a PIPELINE of sub-batches (contiguous ranges of the
-// reads): the handle's host workers check the read words of sub-batch k+1 and move them into pinned staging while
-// sub-batch k's words go up on one copy stream, the kernels of k-1 run on the compute stream, the results of k-2
-// come down on a second copy stream and the workers move those of k-3 out to the caller's arrays.  Buffers the
-// caller has pinned are used as they are (no staging pass).  The results are the ones of the unsplit call: a
-// read's placement does not depend on its batch (tests/test_gpu_parity.py::test_pipeline_equals_unsplit_call).
-extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const uint32_t* read_word,
-                                uint32_t n_reads, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
-                                uint32_t* flags, int32_t* per_node_scores) {
-    if (!mat || !read_off) return set_error(WEPP_EINVAL, "null argument");
-    if (per_node_scores && (uint64_t)n_reads * mat->dev.N > (1ull << 31))
-        return set_error(WEPP_ELIMIT, "per_node_scores: n_reads * n_nodes exceeds 2^31 values; split the batch");
-    if (n_reads == 0) return WEPP_OK;
-    if (read_off[0] != 0) return set_error(WEPP_EINVAL, "read_off[0] must be 0");
-    const uint64_t nw = read_off[n_reads];
-    if (nw && !read_word) return set_error(WEPP_EINVAL, "null read_word");
-    HIP_TRY(hipSetDevice(mat->device));
-    // WEPP_DEBUG_TIMING=1: wall time of the call's phases to stderr
-    const bool dbg_time = mat->tun.debug_timing;
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
-
-    hipError_t e = hipSuccess;
-    if (!mat->pipe_h2d[0]) {
-        for (hipStream_t& st : mat->pipe_h2d)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (hipStream_t& st : mat->pipe_compute)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (hipStream_t& st : mat->pipe_d2h)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (uint32_t i = 0; i < wepp_mat::kPipeMax && e == hipSuccess; i++) {
-            e = hipEventCreateWithFlags(&mat->pipe_up[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&mat->pipe_done[i], hipEventDisableTiming);
-        }
-        for (uint32_t i = 0; i < 4 * wepp_mat::kPipeMax && e == hipSuccess; i++)
-            e = hipEventCreateWithFlags(&mat->pipe_out[i], hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(e, "pipeline streams / events");
-    }
-    // ---- buffers: grow-only, on the handle (no hipMalloc / hipFree per call) ----
-    const size_t off_bytes = (((size_t)(n_reads + 1) * 4) + 255) & ~(size_t)255;
-    const size_t in_need = off_bytes + std::max<size_t>(nw * 4, 16), out_need = (size_t)n_reads * 16;
-    const bool in_pinned = is_pinned_host(read_off) && (nw == 0 || is_pinned_host(read_word));
-    void* dst[4] = {best_bfs_j, score, num_best, flags};
-    bool out_pinned[4];
-    bool any_staged_out = false;
-    for (int i = 0; i < 4; i++) { out_pinned[i] = dst[i] && is_pinned_host(dst[i]); any_staged_out = any_staged_out || (dst[i] && !out_pinned[i]); }
-    {
-        int rc = grow_only(mat->io_in, mat->io_in_bytes, in_need, 4, false, "reads of the batch");
-        if (rc == WEPP_OK) rc = grow_only(mat->io_out, mat->io_out_bytes, out_need, 4, false, "results of the batch");
-        if (rc == WEPP_OK && !in_pinned) rc = grow_only(mat->pin, mat->pin_bytes, in_need, 4, true, "reads of the batch");
-        if (rc == WEPP_OK && any_staged_out) rc = grow_only(mat->pin_out, mat->pin_out_bytes, out_need, 4, true, "results of the batch");
-        if (rc != WEPP_OK) return rc;
-    }
-    uint32_t* const d_off = (uint32_t*)mat->io_in;
-    uint32_t* const d_word = (uint32_t*)((char*)mat->io_in + off_bytes);
-    uint32_t* const d_out = (uint32_t*)mat->io_out;
-    uint32_t* const pin_off = in_pinned ? nullptr : (uint32_t*)mat->pin;
-    uint32_t* const pin_word = in_pinned ? nullptr : (uint32_t*)((char*)mat->pin + off_bytes);
-    uint32_t* const po = (uint32_t*)mat->pin_out;
-
-    // ---- sub-batches and tasks ----
-    const bool big = n_reads >= (1u << 16);
-    if (big && !mat->pool) {
-        // this handle's share of the host threads the process may use (affinity mask and cgroup quota, host_pool.hpp),
-        // one of them being the calling thread: the handles alive now split them (8 device threads of one C++ host
-        // process, or one handle per rank when every rank is a process with its own cpuset); WEPP_HOST_THREADS fixes it
-        const uint32_t share = mat->tun.host_threads ? mat->tun.host_threads
-                                                     : usable_host_threads() / std::max(1u, g_handles_alive.load(std::memory_order_relaxed));
-        mat->pool.reset(new HostPool(std::min<uint32_t>(15, share > 1 ? share - 1 : 1)));
-    }
-    const uint32_t pipe_env = mat->tun.pipe_sub_batches;
-    const uint32_t pipe_knob = mat->pipe_sub_batches ? mat->pipe_sub_batches : pipe_env;
-    // S sub-batches = device calls.  A device call is a chain of ~20 short launches with a host round trip in the
-    // middle (routing counters): ~0.3 ms whatever its size up to a million short reads, most of it the HOST's share,
-    // which two calls cannot overlap -- so a batch is only cut into several calls when each keeps >= 2 M reads
-    // (measured, profiles/r3_experiments/pcie_pipeline.txt: 1 M reads in 2 / 4 / 8 calls 1.41 / 1.98 / 3.07 ms against
-    // 1.28 in one).  C copy chunks >= S: the reads are checked, staged and sent up chunk by chunk, whatever S.
-    // (round 4: with two launch threads a call of half a million reads or more goes as two halves, 1.08 -> 1.00 ms per
-    // 1 M reads; three or four are slower again: the host's HIP calls per device call are what runs out)
-    const bool can_pair = big && mat->pool && mat->pool->workers() >= 2;
-    uint32_t S = !big || per_node_scores ? 1u : pipe_knob ? pipe_knob : std::max<uint32_t>((can_pair && n_reads >= (1u << 19)) ? 2u : 1u, n_reads >> 21);
-    S = std::min<uint32_t>(S, wepp_mat::kPipeMax);
-    const uint32_t min_chunks = mat->tun.pipe_min_chunks;
-    const uint32_t C = big ? S * ((min_chunks + S - 1) / S) : 1;               // copy chunks (a multiple of S, >= 4 unless WEPP_PIPE_MIN_CHUNKS says otherwise)
-    const uint32_t CPS = C / S;                                                // chunks per sub-batch
-    const uint32_t threads = big ? mat->pool->workers() + 1 : 1;
-    const uint32_t PS = big ? std::max(1u, (4 * threads + C - 1) / C) : 1;     // staging parts per chunk
-    const uint32_t PO = big ? 4 : 1;                                           // copy-out parts per (sub-batch, array)
-    // (several sub-batches, every result array wanted and none in memory the caller pinned: one copy per sub-batch)
-    const bool merged_out = S > 1 && dst[0] && dst[1] && dst[2] && dst[3] && !out_pinned[0] && !out_pinned[1] && !out_pinned[2] && !out_pinned[3];
-    auto chunk_lo = [&](uint32_t c) { return (uint32_t)((uint64_t)n_reads * c / C); };
-    auto sub_lo = [&](uint32_t k) { return chunk_lo(k * CPS); };
-    const uint32_t n_stage = C * PS, n_copy = any_staged_out ? S * 4 * PO : 0;
-
-    // preconditions of the reference's merge (usher_mapper.cpp:205-243): sorted, unique positions.  Checked by the
-    // staging tasks, each moving its reads into the pinned staging buffer as it goes (one pass over the input); the
-    // first offending read (lowest index) is reported.
-    // exact, read by read: only run on a range the fast pass below found something in
-    auto check_exact = [&](uint32_t lo, uint32_t hi, uint32_t& bad, int& what) {
-        for (uint32_t r = lo; r < hi; r++) {
-            if (read_off[r + 1] < read_off[r] || read_off[r + 1] > nw) { bad = r; what = 0; return; }
-            for (uint32_t k = read_off[r] + 1; k < read_off[r + 1]; k++)
-                if ((read_word[k] & 0xFFFFFu) <= (read_word[k - 1] & 0xFFFFFu)) { bad = r; what = 1; return; }
-            for (uint32_t k = read_off[r]; k < read_off[r + 1]; k++)
-                if (((read_word[k] >> 24) & 15u) == 0 || ((read_word[k] >> 20) & 15u) == 0) { bad = r; what = 2; return; }
-        }
-    };
-    // fast pass over a range of reads: branch-free loops the compiler vectorises.  Offsets: monotone and inside
-    // the word array.  Words: no zero mask; positions ascend from one word to the next except where a read
-    // starts -- the descents are counted over all words and over the read starts, and must be the same number.
-    auto check = [&](uint32_t lo, uint32_t hi, uint32_t& bad, int& what) {
-        uint32_t off_bad = (read_off[lo] > nw) ? 1u : 0u;
-        for (uint32_t r = lo; r < hi; r++) {
-            const uint32_t a = read_off[r], b = read_off[r + 1];
-            off_bad |= (uint32_t)(b < a) | (uint32_t)(b > nw);
-        }
-        if (off_bad) { check_exact(lo, hi, bad, what); return; }
-        const uint32_t a0 = read_off[lo], b0 = read_off[hi];
-        uint32_t zero = 0, descents = 0, at_starts = 0;
-        if (pin_word) {
-            for (uint32_t k = a0; k < b0; k++) {
-                const uint32_t w = read_word[k];
-                zero |= (uint32_t)(((w >> 24) & 15u) == 0) | (uint32_t)(((w >> 20) & 15u) == 0);
-                pin_word[k] = w;
-            }
-        } else {
-            for (uint32_t k = a0; k < b0; k++) {
-                const uint32_t w = read_word[k];
-                zero |= (uint32_t)(((w >> 24) & 15u) == 0) | (uint32_t)(((w >> 20) & 15u) == 0);
-            }
-        }
-        for (uint32_t k = a0 + 1; k < b0; k++) descents += (uint32_t)((read_word[k] & 0xFFFFFu) <= (read_word[k - 1] & 0xFFFFFu));
-        for (uint32_t r = lo + 1; r < hi; r++) {
-            const uint32_t s0 = read_off[r];
-            if (read_off[r + 1] > s0 && s0 > a0) at_starts += (uint32_t)((read_word[s0] & 0xFFFFFu) <= (read_word[s0 - 1] & 0xFFFFFu));
-        }
-        if (zero || descents != at_starts) check_exact(lo, hi, bad, what);
-    };
-    std::vector<uint32_t> bad(n_stage, 0xFFFFFFFFu);
-    std::vector<int> what(n_stage, 0);
-    std::vector<std::atomic<uint32_t>> staged(C);          // staging parts of a chunk that are done
-    std::vector<std::atomic<int>> launched(S);             // 0: not yet; 1: its D2H is enqueued (pipe_out[k] recorded); -1: never will be
-    for (uint32_t c = 0; c < C; c++) staged[c].store(0);
-    for (uint32_t k = 0; k < S; k++) launched[k].store(0);
-    std::vector<hipError_t> copy_err(std::max<uint32_t>(n_copy, 1), hipSuccess);
-    auto stage_task = [&](uint32_t t) {
-        const uint32_t ck = t / PS, part = t % PS;
-        const uint32_t lo = chunk_lo(ck), hi = chunk_lo(ck + 1);
-        const uint32_t a = lo + (uint32_t)((uint64_t)(hi - lo) * part / PS), b = lo + (uint32_t)((uint64_t)(hi - lo) * (part + 1) / PS);
-        // The offsets this task stages: its reads' [a, b), and -- the LAST part of a chunk -- the chunk's end offset too:
-        // a chunk's H2D copy takes the offsets [first read, last read + 1] and is enqueued as soon as the chunk's OWN
-        // tasks are done.  (Round 3 left the end offset to the first task of the NEXT chunk, which the launch thread
-        // does not wait for: with few host workers the copy went up before it was staged -- a stale or uninitialised
-        // offset for the read at every chunk boundary, wrong entries for that read or a fault in k_route.)  The first
-        // part of a later chunk leaves its first offset to the chunk before: every element has one writer.
-        if (pin_off) {
-            const uint32_t ca = (part == 0 && ck > 0) ? a + 1 : a, cb = (part + 1 == PS) ? b + 1 : b;
-            if (cb > ca) std::memcpy(pin_off + ca, read_off + ca, (size_t)(cb - ca) * 4);
-        }
-        if (b > a) check(a, b, bad[t], what[t]);
-        staged[ck].fetch_add(1, std::memory_order_release);
-    };
-    auto copy_task = [&](uint32_t t) {          // t in [0, n_copy): (sub-batch, array, part)
-        const uint32_t k = t / (4 * PO), i = (t / PO) % 4, part = t % PO;
-        if (!dst[i] || out_pinned[i]) return;
-        int st;
-        while ((st = launched[k].load(std::memory_order_acquire)) == 0) std::this_thread::yield();
-        if (st < 0) return;
-        (void)hipSetDevice(mat->device);                              // (a worker thread starts on device 0)
-        copy_err[t] = hipEventSynchronize(mat->pipe_out[k * 4 + (merged_out ? 0u : i)]);  // this array of the sub-batch has landed (the next one is on the bus)
-        if (copy_err[t] != hipSuccess) return;
-        const size_t lo = sub_lo(k), hi = sub_lo(k + 1);
-        const size_t a = lo + (hi - lo) * part / PO, b = lo + (hi - lo) * (part + 1) / PO;
-        std::memcpy((uint32_t*)dst[i] + a, po + (size_t)i * n_reads + a, (b - a) * 4);
-    };
-    double t_launched = 0;
-
-    // ---- the launch sequence: H2D, kernels, D2H of every sub-batch ----
-    // TWO launchers when the call has several sub-batches and the pool at least two workers: this thread takes the
-    // even sub-batches (lane 0), a pool worker the odd ones (lane 1).  A device call keeps its host thread until its
-    // routing counters are back (place_device polls for them); on one thread the kernels of sub-batch k + 1 were only
-    // enqueued once call k had returned, so the lanes never overlapped (1 M reads in 2 / 4 calls: 1.04 / 1.10 ms against
-    // 1.05 in one).  Every launcher uploads its own sub-batches, the one after the next before the device call of this one.
-    const bool two_launchers = big && S > 1 && mat->pool && mat->pool->workers() >= 2;
-    struct Launcher { int rc = WEPP_OK; std::string msg; };
-    Launcher launcher[2];
-    double t_launch[wepp_mat::kPipeMax] = {};
-    std::atomic<bool> rejected{false};
-    bool up_ok[wepp_mat::kPipeMax] = {};
-    hipError_t up_he[wepp_mat::kPipeMax] = {};
-    // the words of sub-batch k go up chunk by chunk, each as soon as its reads are checked and staged; up_ok[k] = none
-    // of its reads was rejected
-    auto upload = [&](uint32_t k, const Launcher& me) {
-        const uint32_t* src_off = in_pinned ? read_off : pin_off;
-        const uint32_t* src_word = in_pinned ? read_word : pin_word;
-        hipError_t he = hipSuccess;
-        bool ok = me.rc == WEPP_OK && !rejected.load(std::memory_order_acquire);
-        for (uint32_t ck = k * CPS; ck < (k + 1) * CPS && ok && he == hipSuccess; ck++) {
-            while (staged[ck].load(std::memory_order_acquire) < PS) std::this_thread::yield();
-            // (the first offset of a sub-batch is staged with the chunk before it)
-            if (ck == k * CPS && ck > 0) while (staged[ck - 1].load(std::memory_order_acquire) < PS) std::this_thread::yield();
-            for (uint32_t t = ck * PS; t < (ck + 1) * PS && ok; t++) ok = bad[t] == 0xFFFFFFFFu;
-            if (!ok) break;
-            const uint32_t clo = chunk_lo(ck), chi = chunk_lo(ck + 1);
-            const uint32_t w0 = read_off[clo], w1 = read_off[chi];
-            // offset `clo` went up with the chunk before (the kernels of the sub-batch before may be reading it) -- but
-            // the first chunk of a SUB-BATCH sends its own too: the chunk before belongs to the other launcher, whose
-            // copy may not be enqueued yet (the same four bytes written twice)
-            const uint32_t o0 = (ck && ck != k * CPS) ? clo + 1 : clo;
-            he = hipMemcpyAsync(d_off + o0, src_off + o0, (size_t)(chi + 1 - o0) * 4, hipMemcpyHostToDevice, mat->pipe_h2d[k % wepp_mat::kLanes]);
-            if (he == hipSuccess && w1 > w0)
-                he = hipMemcpyAsync(d_word + w0, src_word + w0, (size_t)(w1 - w0) * 4, hipMemcpyHostToDevice, mat->pipe_h2d[k % wepp_mat::kLanes]);
-        }
-        if (ok && he == hipSuccess) he = hipEventRecord(mat->pipe_up[k], mat->pipe_h2d[k % wepp_mat::kLanes]);
-        if (!ok) rejected.store(true, std::memory_order_release);      // nothing of a rejected batch reaches a kernel, and nothing behind it is worth placing
-        up_ok[k] = ok;
-        up_he[k] = he;
-    };
-    auto launch_from = [&](uint32_t first, uint32_t step, Launcher& me) {
-        if (first >= S) return;
-        (void)hipSetDevice(mat->device);                              // (a worker thread starts on device 0)
-        upload(first, me);
-        for (uint32_t k = first; k < S; k += step) {
-            const uint32_t lo = sub_lo(k), hi = sub_lo(k + 1);
-            if (k + step < S) upload(k + step, me);
-            hipError_t he = up_he[k];
-            if (!up_ok[k]) {
-                launched[k].store(-1, std::memory_order_release);
-                continue;
-            }
-            const uint32_t ln = k % wepp_mat::kLanes;             // (sub-batches alternate between the handle's two lanes)
-            hipStream_t cs = mat->pipe_compute[ln];
-            if (he == hipSuccess) he = hipStreamWaitEvent(cs, mat->pipe_up[k], 0);
-            if (he == hipSuccess) {
-                // (the offsets of a sub-batch index the whole call's word array: no rebasing)
-                const int prc = place_device(mat, d_off + lo, d_word, hi - lo, d_out + lo, (int32_t*)(d_out + n_reads) + lo,
-                                             d_out + 2 * (size_t)n_reads + lo, d_out + 3 * (size_t)n_reads + lo, cs, lo, n_reads, ln);
-                if (prc != WEPP_OK) { me.rc = prc; me.msg = wepp_last_error(); launched[k].store(-1, std::memory_order_release); continue; }
-            }
-            if (he == hipSuccess) he = hipEventRecord(mat->pipe_done[k], cs);
-            hipStream_t ds = mat->pipe_d2h[ln];
-            if (he == hipSuccess) he = hipStreamWaitEvent(ds, mat->pipe_done[k], 0);
-            if (merged_out) {
-                // the four result arrays of the sub-batch in ONE (2-D) copy into the staging buffer, which has the device
-                // buffer's layout: a copy and an event are host calls of ~5 us each, and the host's calls are what a
-                // call split into sub-batches runs out of
-                if (he == hipSuccess) he = hipMemcpy2DAsync(po + lo, (size_t)n_reads * 4, d_out + lo, (size_t)n_reads * 4, (size_t)(hi - lo) * 4, 4, hipMemcpyDeviceToHost, ds);
-                if (he == hipSuccess) he = hipEventRecord(mat->pipe_out[k * 4], ds);
-            } else
-            for (int i = 0; i < 4 && he == hipSuccess; i++) {
-                if (!dst[i]) continue;
-                uint32_t* to = out_pinned[i] ? (uint32_t*)dst[i] : po + (size_t)i * n_reads;
-                he = hipMemcpyAsync(to + lo, d_out + (size_t)i * n_reads + lo, (size_t)(hi - lo) * 4, hipMemcpyDeviceToHost, ds);
-                if (he == hipSuccess) he = hipEventRecord(mat->pipe_out[k * 4 + i], ds);   // an array is moved out while the next one comes down
-            }
-            if (he != hipSuccess) {
-                me.rc = hip_fail(he, "H2D / kernels / D2H of a sub-batch");
-                me.msg = wepp_last_error();
-                launched[k].store(-1, std::memory_order_release);
-                continue;
-            }
-            launched[k].store(1, std::memory_order_release);
-            if (dbg_time) t_launch[k] = since();
-        }
-    };
-    {
-        // (the sub-batches' plan ids land in one array sized for the call: grown here, before two threads would)
-        const int prc = S > 1 ? ensure_plan_buffers(mat, n_reads) : WEPP_OK;
-        if (prc != WEPP_OK) return prc;
-        std::lock_guard<std::mutex> lk(mat->stat_mu);
-        mat->plan_reads_in = 0;
-        mat->last_walk_reads = 0;
-        mat->last_n_reads = 0;
-    }
-    if (big) {
-        // two rounds on the pool: the staging tasks (and the second launcher, first in line) while this thread launches;
-        // the copy-out tasks once every sub-batch's copies are enqueued.  (One round of both had the workers that ran
-        // out of staging tasks spin -- yield in a loop -- for their sub-batch's launch: fifteen spinning threads beside
-        // the launch thread, on a container of sixteen cores, delayed the thread they were waiting for.)
-        const uint32_t extra = two_launchers ? 1u : 0u;
-        const std::function<void(uint32_t)> stage_only = [&](uint32_t t) {
-            if (t < extra) launch_from(1, 2, launcher[1]);
-            else stage_task(t - extra);
-        };
-        mat->pool->start(n_stage + extra, stage_only);
-        launch_from(0, two_launchers ? 2 : 1, launcher[0]);
-        mat->pool->finish();
-        if (dbg_time) t_launched = since();
-        if (n_copy) {
-            const std::function<void(uint32_t)> copy_only = [&](uint32_t t) { copy_task(t); };
-            mat->pool->run(n_copy, copy_only);
-        }
-    } else {
-        for (uint32_t t = 0; t < n_stage; t++) stage_task(t);
-        launch_from(0, 1, launcher[0]);
-        for (uint32_t t = 0; t < n_copy; t++) copy_task(t);
-    }
-    int rc = launcher[0].rc != WEPP_OK ? launcher[0].rc : launcher[1].rc;
-    std::string rc_msg = launcher[0].rc != WEPP_OK ? launcher[0].msg : launcher[1].msg;
-    // everything this call put on the handle's streams has finished before it returns -- also after an error, and
-    // when no result array was asked for (the staging buffers belong to the next call then)
-    {
-        hipError_t se = hipSuccess;
-        for (hipStream_t st : {mat->pipe_d2h[0], mat->pipe_d2h[1], mat->pipe_compute[0], mat->pipe_compute[1], mat->pipe_h2d[0], mat->pipe_h2d[1]}) {
-            const hipError_t r = hipStreamSynchronize(st);
-            if (se == hipSuccess) se = r;
-        }
-        if (se != hipSuccess && rc == WEPP_OK) { rc = hip_fail(se, "placement kernels / copies"); rc_msg = wepp_last_error(); }
-    }
-    for (uint32_t t = 0; t < n_stage; t++) {
-        if (bad[t] == 0xFFFFFFFFu) continue;
-        if (what[t] == 0) return set_error(WEPP_EINVAL, "read_off not monotone");
-        if (what[t] == 1)
-            return set_error(WEPP_EINVAL, "read " + std::to_string(bad[t]) + ": entries must be sorted by position with unique positions");
-        return set_error(WEPP_EINVAL, "read " + std::to_string(bad[t]) + ": zero nucleotide mask");
-    }
-    if (rc != WEPP_OK) return set_error(rc, rc_msg);
-    for (uint32_t t = 0; t < n_copy; t++)
-        if (copy_err[t] != hipSuccess) return hip_fail(copy_err[t], "D2H copy of the results");
-    if (per_node_scores) {
-        int32_t* d_pns = nullptr;
-        const size_t nb = (size_t)n_reads * mat->dev.N * sizeof(int32_t);
-        e = hipMalloc((void**)&d_pns, nb);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc per_node_scores: ") + hipGetErrorString(e));
-        e = launch_scores(mat->dev, mat->streams.back(), d_off, d_word, n_reads, d_pns, nullptr);   // (everything above has been synchronised)
-        if (e == hipSuccess) e = hipMemcpy(per_node_scores, d_pns, nb, hipMemcpyDeviceToHost);
-        (void)hipFree(d_pns);
-        if (e != hipSuccess) return hip_fail(e, "per-node score kernel");
-    }
-    if (dbg_time) {
-        fprintf(stderr, "[place_batch] %u reads in %u sub-batches (%s in, %s out): D2H of sub-batch k enqueued at", n_reads, S,
-                in_pinned ? "caller-pinned" : "staged", any_staged_out ? "staged" : "caller-pinned");
-        for (uint32_t k = 0; k < S; k++) fprintf(stderr, " %.3f", t_launch[k]);
-        fprintf(stderr, " ms; every launch enqueued at %.3f ms; total %.3f ms\n", t_launched, since());
-    }
-    return WEPP_OK;
-}
-
-namespace {
-
-// shared argument check of the calls that take a read CSR from the host: offsets start at 0, are monotone and
-// stay inside the word array (whose size is read_off[n_reads])
-int check_read_csr(const uint32_t* read_off, const uint32_t* read_word, uint32_t n_reads) {
-    if (!read_off) return set_error(WEPP_EINVAL, "null read_off");
-    if (read_off[0] != 0) return set_error(WEPP_EINVAL, "read_off[0] must be 0");
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (read_off[r + 1] < read_off[r]) return set_error(WEPP_EINVAL, "read_off not monotone");
-    if (read_off[n_reads] && !read_word) return set_error(WEPP_EINVAL, "null read_word");
-    return WEPP_OK;
-}
-
-// Grow-only buffers of the handle for the pass-2 calls: `dev_bytes` of device memory in io_in and `pin_bytes`
-// of pinned staging (the same buffers wepp_place_batch uses; the calls on a handle are serial).
-int reserve_io(wepp_mat* mat, size_t dev_bytes, size_t pin_need) {
-    const int rc = grow_only(mat->io_in, mat->io_in_bytes, dev_bytes, 4, false, "io buffer");
-    return rc != WEPP_OK ? rc : grow_only(mat->pin, mat->pin_bytes, pin_need, 4, true, "staging buffer");
-}
-
-}  // namespace
-
-extern "C" int wepp_imputed_mutations(wepp_mat_t* mat, const uint32_t* read_off, const uint32_t* read_word,
-                                      uint32_t n_reads, const uint32_t* best_bfs_j, uint32_t* imp_off,
-                                      int32_t* imp_pos, uint8_t* imp_nuc, uint64_t capacity) {
-    if (!mat || !read_off || !best_bfs_j || !imp_off) return set_error(WEPP_EINVAL, "null argument");
-    {
-        int rc = check_read_csr(read_off, read_word, n_reads);
-        if (rc != WEPP_OK) return rc;
-    }
-    std::vector<uint32_t> pairs;
-    imp_off[0] = 0;
-    for (uint32_t r = 0; r < n_reads; r++) {
-        if (best_bfs_j[r] >= mat->dev.N) return set_error(WEPP_EINVAL, "best_bfs_j out of range");
-        for (uint32_t k = read_off[r]; k < read_off[r + 1]; k++) {
-            const uint32_t w = read_word[k], a = (w >> 24) & 15u;
-            if (!((w >> 28) & 1u) && (a & (a - 1))) { pairs.push_back(r); pairs.push_back(k); }
-        }
-        imp_off[r + 1] = (uint32_t)(pairs.size() / 2);
-    }
-    const uint32_t np = (uint32_t)(pairs.size() / 2);
-    if (np > capacity) return set_error(WEPP_ELIMIT, "imputed-mutation buffers too small: need " + std::to_string(np));
-    if (np == 0) return WEPP_OK;
-    if (!imp_pos || !imp_nuc) return set_error(WEPP_EINVAL, "null argument");
-    for (uint32_t i = 0; i < np; i++) imp_pos[i] = (int32_t)(read_word[pairs[2 * i + 1]] & 0xFFFFFu);
-    HIP_TRY(hipSetDevice(mat->device));
-    // one staged upload (offsets | words | placements | pairs) and one download (nucleotides) through the
-    // handle's pinned buffer; device memory from its grow-only input buffer
-    const uint64_t nw = read_off[n_reads];
-    const size_t b_off = pad256((size_t)(n_reads + 1) * 4), b_word = pad256(std::max<size_t>(nw * 4, 16));
-    const size_t b_best = pad256((size_t)n_reads * 4), b_pairs = pad256((size_t)np * 8), b_nuc = pad256(np);
-    const size_t up = b_off + b_word + b_best + b_pairs;
-    {
-        int rc = reserve_io(mat, up + b_nuc, up);
-        if (rc != WEPP_OK) return rc;
-    }
-    char* hp = (char*)mat->pin;
-    std::memcpy(hp, read_off, (size_t)(n_reads + 1) * 4);
-    if (nw) std::memcpy(hp + b_off, read_word, nw * 4);
-    std::memcpy(hp + b_off + b_word, best_bfs_j, (size_t)n_reads * 4);
-    std::memcpy(hp + b_off + b_word + b_best, pairs.data(), (size_t)np * 8);
-    char* dp = (char*)mat->io_in;
-    HIP_TRY(hipMemcpy(dp, hp, up, hipMemcpyHostToDevice));
-    uint8_t* d_nuc = (uint8_t*)(dp + up);
-    HIP_TRY(launch_imputed(mat->dev, (const uint32_t*)dp, (const uint32_t*)(dp + b_off), (const uint32_t*)(dp + b_off + b_word),
-                           (const uint32_t*)(dp + b_off + b_word + b_best), np, d_nuc, nullptr));
-    hipError_t e = hipMemcpy(hp, d_nuc, np, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "imputed-mutation kernel");
-    std::memcpy(imp_nuc, hp, np);
-    return WEPP_OK;
-}
-
-extern "C" int wepp_excess_mutations(wepp_mat_t* mat, const uint32_t* read_off, const uint32_t* read_word,
-                                     uint32_t n_reads, uint32_t n_pairs, const uint32_t* pair_read,
-                                     const uint32_t* pair_bfs_j, uint64_t* exc_off, int32_t* exc_pos, uint8_t* exc_ref,
-                                     uint8_t* exc_par, uint8_t* exc_mut, uint64_t capacity) {
-    if (!mat || !read_off || !exc_off) return set_error(WEPP_EINVAL, "null argument");
-    exc_off[0] = 0;
-    if (n_pairs == 0) return WEPP_OK;
-    if (!pair_read || !pair_bfs_j) return set_error(WEPP_EINVAL, "null argument");
-    {
-        int rc = check_read_csr(read_off, read_word, n_reads);
-        if (rc != WEPP_OK) return rc;
-    }
-    for (uint32_t i = 0; i < n_pairs; i++) {
-        if (pair_read[i] >= n_reads) return set_error(WEPP_EINVAL, "pair_read out of range");
-        if (pair_bfs_j[i] >= mat->dev.N) return set_error(WEPP_EINVAL, "pair_bfs_j out of range");
-    }
-    const uint64_t nw = read_off[n_reads];
-    HIP_TRY(hipSetDevice(mat->device));
-    // upload (offsets | words | pair reads | pair nodes), count, size the output, emit: all through the
-    // handle's grow-only device buffer and pinned staging buffer
-    const size_t b_off = pad256((size_t)(n_reads + 1) * 4), b_word = pad256(std::max<size_t>(nw * 4, 16));
-    const size_t b_pair = pad256((size_t)n_pairs * 4), b_ooff = pad256((size_t)n_pairs * 8);
-    const size_t up = b_off + b_word + 2 * b_pair;
-    const size_t fixed = up + b_pair /* counts */ + b_ooff;
-    {
-        int rc = reserve_io(mat, fixed, std::max(up, b_ooff));
-        if (rc != WEPP_OK) return rc;
-    }
-    char* hp = (char*)mat->pin;
-    std::memcpy(hp, read_off, (size_t)(n_reads + 1) * 4);
-    if (nw) std::memcpy(hp + b_off, read_word, nw * 4);
-    std::memcpy(hp + b_off + b_word, pair_read, (size_t)n_pairs * 4);
-    std::memcpy(hp + b_off + b_word + b_pair, pair_bfs_j, (size_t)n_pairs * 4);
-    char* dp = (char*)mat->io_in;
-    HIP_TRY(hipMemcpy(dp, hp, up, hipMemcpyHostToDevice));
-    const uint32_t *d_off = (const uint32_t*)dp, *d_word = (const uint32_t*)(dp + b_off);
-    const uint32_t *d_pr = (const uint32_t*)(dp + b_off + b_word), *d_pj = (const uint32_t*)(dp + b_off + b_word + b_pair);
-    uint32_t* d_cnt = (uint32_t*)(dp + up);
-    unsigned long long* d_ooff = (unsigned long long*)(dp + up + b_pair);
-    HIP_TRY(launch_excess(mat->dev, d_off, d_word, d_pr, d_pj, n_pairs, nullptr, d_cnt, nullptr, nullptr));
-    hipError_t e = hipMemcpy(hp, d_cnt, (size_t)n_pairs * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "excess-mutation count");
-    uint64_t total = 0;
-    {
-        const uint32_t* counts = (const uint32_t*)hp;
-        for (uint32_t i = 0; i < n_pairs; i++) { total += counts[i]; exc_off[i + 1] = total; }
-    }
-    if (total > capacity) return set_error(WEPP_ELIMIT, "excess-mutation buffers too small: need " + std::to_string(total));
-    if (total == 0) return WEPP_OK;
-    if (!exc_pos || !exc_ref || !exc_par || !exc_mut) return set_error(WEPP_EINVAL, "null output array");
-    {
-        // the device buffer may move when it grows: the inputs are uploaded again behind the new base
-        const bool grows = fixed + pad256(total * 4) > mat->io_in_bytes;
-        int rc = reserve_io(mat, fixed + pad256(total * 4), std::max({up, b_ooff, (size_t)total * 4}));
-        if (rc != WEPP_OK) return rc;
-        hp = (char*)mat->pin;
-        if (grows) {
-            std::memcpy(hp, read_off, (size_t)(n_reads + 1) * 4);
-            if (nw) std::memcpy(hp + b_off, read_word, nw * 4);
-            std::memcpy(hp + b_off + b_word, pair_read, (size_t)n_pairs * 4);
-            std::memcpy(hp + b_off + b_word + b_pair, pair_bfs_j, (size_t)n_pairs * 4);
-            dp = (char*)mat->io_in;
-            HIP_TRY(hipMemcpy(dp, hp, up, hipMemcpyHostToDevice));
-            d_off = (const uint32_t*)dp; d_word = (const uint32_t*)(dp + b_off);
-            d_pr = (const uint32_t*)(dp + b_off + b_word); d_pj = (const uint32_t*)(dp + b_off + b_word + b_pair);
-            d_cnt = (uint32_t*)(dp + up);
-            d_ooff = (unsigned long long*)(dp + up + b_pair);
-        }
-    }
-    {
-        unsigned long long* ho = (unsigned long long*)hp;
-        for (uint32_t i = 0; i < n_pairs; i++) ho[i] = exc_off[i];
-        HIP_TRY(hipMemcpy(d_ooff, ho, (size_t)n_pairs * 8, hipMemcpyHostToDevice));
-    }
-    uint32_t* d_out = (uint32_t*)(dp + fixed);
-    HIP_TRY(launch_excess(mat->dev, d_off, d_word, d_pr, d_pj, n_pairs, d_ooff, d_cnt, d_out, nullptr));
-    e = hipMemcpy(hp, d_out, total * 4, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(e, "excess-mutation kernel");
-    const uint32_t* packed = (const uint32_t*)hp;
-    for (uint64_t q = 0; q < total; q++) {
-        exc_pos[q] = (int32_t)(packed[q] & 0xFFFFFu);
-        exc_ref[q] = (uint8_t)((packed[q] >> 20) & 15u);
-        exc_par[q] = (uint8_t)((packed[q] >> 24) & 15u);
-        exc_mut[q] = (uint8_t)((packed[q] >> 28) & 15u);
-    }
-    return WEPP_OK;
-}
-
-// best_j_vec: every optimal node of every read (usher_common.cpp:376-381, 413-446)
-extern "C" int wepp_best_nodes(wepp_mat_t* mat, const uint32_t* read_off, const uint32_t* read_word, uint32_t n_reads,
-                               const int32_t* score, const uint32_t* num_best, uint64_t* best_off, uint32_t* best_nodes,
-                               uint64_t capacity) {
-    if (!mat || !read_off || !score || !num_best || !best_off) return set_error(WEPP_EINVAL, "null argument");
-    {
-        int rc = check_read_csr(read_off, read_word, n_reads);
-        if (rc != WEPP_OK) return rc;
-    }
-    best_off[0] = 0;
-    for (uint32_t r = 0; r < n_reads; r++) best_off[r + 1] = best_off[r] + num_best[r];
-    const uint64_t total = best_off[n_reads];
-    if (total > capacity) return set_error(WEPP_ELIMIT, "best-node list too small: need " + std::to_string(total));
-    if (n_reads == 0 || total == 0) return WEPP_OK;
-    if (!best_nodes) return set_error(WEPP_EINVAL, "null argument");
-    if (total >= (1ull << 32)) return set_error(WEPP_ELIMIT, "more than 2^32 optimal nodes in one call; split the batch");
-    const uint64_t nw = read_off[n_reads];
-    HIP_TRY(hipSetDevice(mat->device));
-    // device buffers (grow-only io_in): offsets | words | scores | CSR offsets | cursors | routing arrays | the list
-    const size_t b_off = pad256((size_t)(n_reads + 1) * 4), b_word = pad256(std::max<size_t>(nw * 4, 16));
-    const size_t b_r = pad256((size_t)n_reads * 4), b_o64 = pad256((size_t)(n_reads + 1) * 8), b_r1 = pad256(n_reads);
-    const size_t up = b_off + b_word + b_r + b_o64;                       // uploaded in one staged copy
-    const size_t fixed = up + b_r /* cursors */ + b_r1 /* plan ids */ + 4 * b_r /* list, root score, slot, jobs */;
-    {
-        int rc = reserve_io(mat, fixed + pad256(total * 4), std::max(up, (size_t)total * 4));
-        if (rc != WEPP_OK) return rc;
-    }
-    char* hp = (char*)mat->pin;
-    std::memcpy(hp, read_off, (size_t)(n_reads + 1) * 4);
-    if (nw) std::memcpy(hp + b_off, read_word, nw * 4);
-    std::memcpy(hp + b_off + b_word, score, (size_t)n_reads * 4);
-    std::memcpy(hp + b_off + b_word + b_r, best_off, (size_t)(n_reads + 1) * 8);
-    char* dp = (char*)mat->io_in;
-    HIP_TRY(hipMemcpy(dp, hp, up, hipMemcpyHostToDevice));
-    const uint32_t *d_off = (const uint32_t*)dp, *d_word = (const uint32_t*)(dp + b_off);
-    const int32_t* d_best = (const int32_t*)(dp + b_off + b_word);
-    const unsigned long long* d_o64 = (const unsigned long long*)(dp + b_off + b_word + b_r);
-    char* q = dp + up;
-    uint32_t* d_cursor = (uint32_t*)q; q += b_r;
-    uint8_t* d_plan = (uint8_t*)q; q += b_r1;
-    uint32_t* d_list = (uint32_t*)q; q += b_r;
-    int32_t* d_root = (int32_t*)q; q += b_r;
-    uint32_t* d_slot = (uint32_t*)q; q += b_r;
-    uint32_t* d_jobs = (uint32_t*)q; q += b_r;
-    uint32_t* d_nodes = (uint32_t*)q;
-    HIP_TRY(hipMemsetAsync(d_cursor, 0, (size_t)n_reads * 4, nullptr));
-    // the stream of every read: the routing of a placement call with the walks off.  A read inside one genome window
-    // lists its nodes on the window's stream when that is the window's candidate crown (real nodes only, a few
-    // thousand of them whatever the read's root score: device_mat.hpp win_n) and smaller than the tree-wide stream of
-    // its theta; a whole-tree window stream folds runs of nodes into pseudo-nodes: nothing to list there
-    DevMAT dm = mat->dev;
-    dm.wc_windows = 0;            // (no per-read window crowns: k_scores takes one stream per launch)
-    uint32_t* tier_info = mat->lane[0].d_info + mat->lane[0].info_idx * TI_WORDS;
-    uint32_t* tier_info_next = mat->lane[0].d_info + (mat->lane[0].info_idx ^ 1u) * TI_WORDS;
-    uint32_t* blk_counts = mat->lane[0].d_info + 2 * TI_WORDS;
-    HIP_TRY(launch_route(dm, d_off, d_word, n_reads, mat->use_crowns ? 3 : 0, 0u, WALK_JOB_EVENTS | (WALK_JOB_EVENTS << 16), WALK8_ROWS, WALK16_ROWS,
-                         0xFFFFFFFFu, 0u, d_jobs, d_plan, d_root, blk_counts, tier_info, d_slot, tier_info_next, d_jobs, RouteDirect{}, nullptr));
-    mat->lane[0].info_idx ^= 1u;
-    HIP_TRY(launch_scatter(d_plan, d_slot, n_reads, blk_counts, tier_info, d_list, false, nullptr));
-    HIP_TRY(hipMemcpy(mat->lane[0].h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    const uint32_t* info = mat->lane[0].h_info;
-    const bool debug_plans = mat->tun.debug_plans;
-    for (uint32_t id = 0; id < MAX_PLANS; id++) {
-        const uint32_t count = info[TI_COUNT + id];
-        if (!count) continue;
-        const bool win = plan_class(id) == PLAN_WIN;
-        if (win ? (plan_index(id) >= mat->wstreams.size() || mat->wstreams[plan_index(id)].ncnt != nullptr)
-                : (plan_class(id) != PLAN_SWEEP || plan_index(id) >= mat->streams.size()))
-            return set_error(WEPP_EDEVICE, "routing produced an invalid plan id");
-        if (debug_plans) fprintf(stderr, "[best_nodes] %s %u: %u reads\n", win ? "window" : "stream", plan_index(id), count);
-        HIP_TRY(launch_best_nodes(mat->dev, win ? mat->wstreams[plan_index(id)] : mat->streams[plan_index(id)], d_off, d_word,
-                                  d_list + info[TI_OFF + id], count, d_best, d_o64, d_cursor, d_nodes, nullptr));
-    }
-    {
-        hipError_t e = hipMemcpy(hp, d_nodes, total * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "best-node kernel");
-        std::vector<uint32_t> taken(n_reads);
-        e = hipMemcpy(taken.data(), d_cursor, (size_t)n_reads * 4, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hip_fail(e, "best-node kernel");
-        for (uint32_t r = 0; r < n_reads; r++)
-            if (taken[r] != num_best[r])
-                return set_error(WEPP_EINVAL, "read " + std::to_string(r) + ": score / num_best are not this read's placement on this tree (" +
-                                              std::to_string(taken[r]) + " nodes attain the score, num_best says " + std::to_string(num_best[r]) + ")");
-    }
-    std::memcpy(best_nodes, hp, total * 4);
-    // (the kernel fills a read's slice in the order its waves get there: ascending BFS index is the contract)
-    for (uint32_t r = 0; r < n_reads; r++)
-        if (num_best[r] > 1) std::sort(best_nodes + best_off[r], best_nodes + best_off[r + 1]);
     return WEPP_OK;
 }
 

@@ -1,5 +1,5 @@
-// handle.hpp -- the object behind wepp_mat_t and the small helpers the C-ABI translation units (capi.cpp and
-// the *_capi.cpp of the WEPP entry points) share.  It compiles against the emulated runtime of tests/cxx/hip_emu too:
+// handle.hpp -- the object behind wepp_mat_t and the small helpers the C-ABI translation units (capi.cpp,
+// place_batch.cpp and the *_capi.cpp of the entry points) share.  It compiles against the emulated runtime of tests/cxx/hip_emu too:
 // tests/epp_emu.py runs the entry points' own host code on a handle made there.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -186,5 +186,21 @@ inline int upload(wepp_mat* h, const std::vector<T>& v, const T** out) {
     *out = (const T*)p;
     return WEPP_OK;
 }
+
+// a call that returns a WEPP_* code: anything but WEPP_OK is the caller's return value too
+#define WEPP_TRY(expr)                     \
+    do {                                   \
+        const int _rc = (expr);            \
+        if (_rc != WEPP_OK) return _rc;    \
+    } while (0)
+
+// defined in capi.cpp, used by place_batch.cpp and pass2_capi.cpp too
+uint32_t handles_alive();             // handles alive in this process
+size_t pad256(size_t b);
+int grow_only(void*& p, size_t& have, size_t need, size_t slack, bool pinned, const char* what);
+int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total);
+int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
+                 uint32_t* d_best_bfs_j, int32_t* d_score, uint32_t* d_num_best, uint32_t* d_flags, hipStream_t stream,
+                 uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx = 0);
 
 }  // namespace wepp
