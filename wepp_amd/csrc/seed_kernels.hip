@@ -42,6 +42,7 @@ namespace {
 constexpr uint32_t SEED_WAVES = SEED_THREADS / 64;
 constexpr uint32_t SEED_SHARED_WORDS = 16 + 3 * SEED_WAVES;   // bound, counters, largest count, per-wave partials
 constexpr uint32_t SEED_HIT_CAP = 96;                         // hit events of a group of blocks a wave lists before it evaluates them
+// (96 listed / 97 block by block, in one block and spread over a group: tests/test_seed_edges_gpu.py, cases hits_one_block and groups_*)
 // LDS (dwords): position bitmap [bm_words] | the sample's words [ent_cap] | hard entries [SEED_MAX_HARD + 1] |
 // per-chunk counters, one byte each, [chunks rounded up to 64] | shared scalars | per wave: hit list [3 * SEED_HIT_CAP]
 __host__ __device__ inline uint32_t seed_h_words(uint32_t chunks) { return ((chunks + 63) & ~63u) / 4; }
@@ -268,6 +269,7 @@ __global__ __launch_bounds__(SEED_THREADS) void k_seed(DevMAT m, DevStream full,
         // groups of up to 32 blocks: their event offsets and summaries are fetched together (lane = block), their
         // events are scanned for positions of the sample eight loads at a time (lane = event) -- the chunk's memory
         // round trips are a handful instead of four per block
+        // (groups of exactly 32 blocks, tail groups, more than 512 events: tests/test_seed_edges_gpu.py, cases groups_32 / _33 / _40)
         for (uint32_t bg = b0; bg < b1; bg += 32) {
             const uint32_t ng = min(32u, b1 - bg);
             const uint32_t eo = lane <= ng ? full.blk_eoff[bg + lane] : 0u;
