@@ -759,6 +759,45 @@ int wepp_sam_fetch_words(uint32_t *read_word, uint64_t capacity);
  * the correction (word counts, their scan, the words); the sort; the merge (flags, scans, the merged batch) */
 int wepp_sam_last_timing(double *pileup_ms, double *correct_ms, double *sort_ms, double *merge_ms);
 
+/* ---- pairwise distances between genotypes (haplotype uncertainty, truth report) ---- *
+ * The primitive behind dump_haplotype_uncertainty (src/WEPP/arena.cpp:494-528) and print_mutation_distance
+ * (:251-301): mutation_distance over get_mutations (src/WEPP/util.cpp:188-222, 271-296), taken over all pairs of a
+ * group or over A x B.  No tree handle: the calls run on HIP device `device`; the caller lists the genotypes.
+ * A genotype is the list of a node's differences from the reference: one word wepp_pack_read_word(position, ref_nuc,
+ * mut_nuc, 0) per position where the deepest mutation on the node's root path leaves mut_nuc != ref_nuc, ascending by
+ * position.  d(a, b) = the number of positions at which the two lists differ, "no entry" being a value of its own:
+ * masks are compared for equality (an ambiguous mask or 15 is one more value), two different alleles at one position
+ * count 1, d is symmetric; it is the Hamming distance of the vectors of 4-bit masks with "no entry" written 0000.
+ * keep_bits (or NULL: every position is kept) restricts both lists first, as print_mutation_distance does with
+ * site_read_map: position p is kept when p < keep_positions and bit p & 31 of keep_bits[p / 32] is set.
+ * wepp_geno_diameters: group k = the items grp_off[k] .. grp_off[k + 1]; diam[k] = the largest d of two of its items,
+ *   0 for a group of 0 or 1 items.  n_groups == 0: WEPP_OK.
+ * wepp_geno_nearest: items [0, n_a) are A, the rest B; min_dist[a] = the least d(a, b), nearest[a] = the lowest index
+ *   into B attaining it; matrix (or NULL) receives d(a, b) at [a * n_b + b].
+ * On the device every item becomes four bit-planes over the distinct kept positions of its group (of A and B
+ * together); the planes of the groups are worked off in passes of consecutive groups holding at most 1 GiB of planes
+ * (GENO_PASS_BYTES, wepp_amd/csrc/geno.hpp).  WEPP_GENO_PASS_BYTES in the environment (diagnostic, read once per call,
+ * changes no result) lowers that bound; a single group, or A and B together, beyond 1 GiB is WEPP_ELIMIT.
+ * Results are bit-identical from run to run.
+ * WEPP_EINVAL: a null argument, positions of an item not strictly ascending, mut_nuc == ref_nuc or mut_nuc == 0, bits
+ * above mut_nuc set, a position above WEPP_MAX_POSITION, item_off[0] / grp_off[0] != 0 or offsets that do not ascend,
+ * grp_off that does not end at n_items, n_a == 0 or an empty B.  WEPP_ELIMIT besides: n_items >= 2^31, 2^32 or more
+ * words, a matrix of more than 2^28 cells. */
+typedef struct {
+    uint32_t n_items;
+    const uint64_t *item_off;    /* [n_items + 1] */
+    const uint32_t *item_word;   /* wepp_pack_read_word(pos, ref, mut, 0): sorted by position, positions unique,
+                                    mut != ref, mut in 1..15 */
+} wepp_genotypes;
+int wepp_geno_diameters(int device, const wepp_genotypes *g, const uint32_t *keep_bits, uint32_t keep_positions,
+                        uint32_t n_groups, const uint32_t *grp_off /* [n_groups + 1] over the items */, int32_t *diam);
+int wepp_geno_nearest(int device, const wepp_genotypes *g, uint32_t n_a, const uint32_t *keep_bits,
+                      uint32_t keep_positions, int32_t *min_dist /* [n_a] */, uint32_t *nearest /* [n_a] */,
+                      int32_t *matrix /* [n_a * n_b] or NULL */);
+/* device time of the calling thread's last wepp_geno_diameters / wepp_geno_nearest by phase (HIP events, ms, summed
+ * over the passes): the columns (keys, sort, scan); the planes; the pairs */
+int wepp_geno_last_timing(double *columns_ms, double *planes_ms, double *pairs_ms);
+
 /* ---- host-side introspection of the flattened MAT (no GPU needed) -------- *
  * Lets the CPU test-suite check the flattener (orders, parent alleles, per-node
  * constants, event stream) against the oracle.  `name` is one of: node_woff,

@@ -171,6 +171,10 @@ class SamOutC(ctypes.Structure):
                 ("degree", ctypes.c_void_p), ("word_capacity", ctypes.c_uint64)]
 
 
+class GenotypesC(ctypes.Structure):
+    _fields_ = [("n_items", ctypes.c_uint32), ("item_off", ctypes.c_void_p), ("item_word", ctypes.c_void_p)]
+
+
 # every symbol include/wepp_place.h declares (tests/test_abi.py checks the list
 # against the header)
 _V = ctypes.c_void_p
@@ -240,6 +244,9 @@ _SIGS = {
                                       ctypes.POINTER(SamOutC)]),
     "wepp_sam_fetch_words": (ctypes.c_int, [_V, ctypes.c_uint64]),
     "wepp_sam_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
+    "wepp_geno_diameters": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GenotypesC), _V, ctypes.c_uint32, ctypes.c_uint32, _V, _V]),
+    "wepp_geno_nearest": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GenotypesC), ctypes.c_uint32, _V, ctypes.c_uint32, _V, _V, _V]),
+    "wepp_geno_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
     "wepp_last_error": (ctypes.c_char_p, []),
     "wepp_gen_tree_create": (ctypes.c_int, [ctypes.POINTER(GenTreeParams), ctypes.POINTER(_V)]),
     "wepp_gen_tree_desc": (ctypes.c_int, [_V, ctypes.POINTER(TreeDescC)]),

@@ -3,7 +3,7 @@
 // `wepp sam2PB`) + reference FASTA [+ mask.bed] -> haplotype scores and per-read placements.
 //   wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--dump] [--assign FILE [--resolve RESIDUAL]]
 //            [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]]
-//            [--clade-idx N]
+//            [--clade-idx N] [--uncertainty] [--haplotypes] [--truth TRUE]   (the last three with --assign only)
 // --dump prints what the loaders and the condensing step produced and exits (no GPU needed).
 // Output: <outdir>/haplotype_scores.tsv (arena order: id, score, dist_divergence, sources),
 //         <outdir>/read_placements.tsv  (read, start, end, degree, parsimony, epps).
@@ -54,6 +54,21 @@
 //                                          equal sums go by ascending name.
 // N beyond the last column prints the reference's error line (arena.cpp:458): the lineage column stays empty and
 // lineage_proportion.csv has no rows.  With --dump, --clade-idx prints `lineage <haplotype>\t<name>` for every haplotype.
+// --uncertainty (with --assign only): arena::dump_haplotype_uncertainty (arena.cpp:494-528)
+//         <outdir>/haplotype_uncertainty.csv one row per selected haplotype in the order of FILE: max_dist,id,id,... --
+//                                          the nodes of the full tree that were merged into its condensed node (they
+//                                          differ only at sites no read covers), in the order of node_mappings, and the
+//                                          largest mutation distance between two of them: one wepp_geno_diameters call
+//                                          for the whole selection.
+// --haplotypes (with --assign only): arena::dump_haplotypes (arena.cpp:906-931)
+//         <outdir>/haplotypes.tsv          one SAM-like row per selected haplotype in the order of FILE: id, 0, the first
+//                                          token of the FASTA header, 1, 60, <len>M, *, 0, 0, the haplotype's sequence,
+//                                          <len> x '?', MD:Z:..., RG:Z:group.  Host code, no kernel.
+// --truth TRUE (with --assign only): arena::print_mutation_distance (arena.cpp:251-301) for simulated data.  TRUE holds
+// one identifier of a node of the full tree per line (an unknown or repeated identifier is an error).  Printed to
+// stdout: `--- ground truth <n> haps; predicted <k> haps`, per true node `* dist: %02d true_node: <id> pred_node: <id> `
+// -- the least mutation distance to a selected haplotype, both genotypes restricted to the sites a read covers
+// (site_read_map), and the first haplotype of FILE attaining it (wepp_geno_nearest) -- and `average mutation_distance: %0.3f`.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -62,10 +77,59 @@
 #include <string>
 #include <unordered_set>
 
+#include "../../include/wepp_place.h"
+#include "haplotype_report.hpp"
 #include "wepp_filter.hpp"
 
+// dump_haplotype_uncertainty's distances (arena.cpp:503-516) in one wepp_geno_diameters call: max_dist[k] = the largest
+// mutation_distance between the genotypes of two of node_mappings[selected[k]] (nodes of the full tree), 0 for one source
+static int haplotype_uncertainty(const std::vector<MAT::Node*>& selected, const std::unordered_map<MAT::Node*, std::vector<MAT::Node*>>& node_mappings,
+                                 std::vector<int>& max_dist, int device) {
+    genotype_lister lister;
+    packed_genotypes items;
+    std::vector<uint32_t> grp_off{0};
+    for (MAT::Node* hap : selected) {
+        for (const MAT::Node* src : node_mappings.at(hap)) items.add(lister.get_mutations(src));
+        grp_off.push_back(items.size());
+    }
+    const wepp_genotypes g{items.size(), items.item_off.data(), items.item_word.data()};
+    std::vector<int32_t> diam(selected.size(), 0);
+    if (wepp_geno_diameters(device, &g, nullptr, 0, (uint32_t)selected.size(), grp_off.data(), diam.data()) != WEPP_OK) {
+        fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+        return 1;
+    }
+    max_dist.assign(diam.begin(), diam.end());
+    return 0;
+}
+
+// print_mutation_distance's minima (arena.cpp:258-294) in one wepp_geno_nearest call: for every node of true_nodes the
+// least mutation_distance to a node of `predicted` (full-tree nodes: the first source of every selected haplotype),
+// both genotypes restricted to `sites`, and the first node of `predicted` attaining it
+static int truth_distances(const std::vector<MAT::Node*>& true_nodes, const std::vector<MAT::Node*>& predicted, const std::unordered_set<int>& sites,
+                           std::vector<int>& min_dist, std::vector<int>& nearest, int device) {
+    genotype_lister lister;
+    packed_genotypes items;
+    for (const MAT::Node* n : true_nodes) items.add(lister.get_mutations(n));
+    for (const MAT::Node* n : predicted) items.add(lister.get_mutations(n));
+    uint32_t keep_positions = 0;
+    const std::vector<uint32_t> keep = keep_bits_of(sites, &keep_positions);
+    const uint32_t none = 0;                                              // (no site is covered: an empty mask, not "keep all")
+    const wepp_genotypes g{items.size(), items.item_off.data(), items.item_word.data()};
+    std::vector<int32_t> md(true_nodes.size(), 0);
+    std::vector<uint32_t> nr(true_nodes.size(), 0);
+    if (wepp_geno_nearest(device, &g, (uint32_t)true_nodes.size(), keep.empty() ? &none : keep.data(), keep_positions, md.data(), nr.data(), nullptr) !=
+        WEPP_OK) {
+        fprintf(stderr, "ERROR: %s\n", wepp_last_error());
+        return 1;
+    }
+    min_dist.assign(md.begin(), md.end());
+    nearest.assign(nr.begin(), nr.end());
+    return 0;
+}
+
 int main(int argc, char** argv) {
-    std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, neighbors_f, outdir = ".";
+    std::string mat_f, reads_f, ref_f, mask_f, assign_f, resolve_f, neighbors_f, truth_f, outdir = ".";
+    bool want_uncertainty = false, want_haplotypes = false;
     int device = 0, radius = 2, max_neighbors = 500;       // config.hpp:24-25
     int clade_idx = -1;                                     // --clade-idx: -1 = not given
     peaks_params peak_par;
@@ -88,6 +152,9 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--radius")) radius = atoi(need("--radius"));
         else if (!strcmp(argv[i], "--max-neighbors")) max_neighbors = atoi(need("--max-neighbors"));
         else if (!strcmp(argv[i], "--peaks")) want_peaks = true;
+        else if (!strcmp(argv[i], "--uncertainty")) want_uncertainty = true;
+        else if (!strcmp(argv[i], "--haplotypes")) want_haplotypes = true;
+        else if (!strcmp(argv[i], "--truth")) truth_f = need("--truth");
         else if (!strcmp(argv[i], "--top-n")) peak_par.top_n = atoi(need("--top-n"));
         else if (!strcmp(argv[i], "--max-peaks")) peak_par.max_peaks = atoi(need("--max-peaks"));
         else if (!strcmp(argv[i], "--peak-radius")) peak_par.peak_radius = atoi(need("--peak-radius"));
@@ -98,14 +165,18 @@ int main(int argc, char** argv) {
             if (endp == v || *endp != '\0' || n < 0 || n > 1000000) { fprintf(stderr, "ERROR: --clade-idx needs a column number (0, 1, ...), got '%s'\n", v); return 1; }
             clade_idx = (int)n;
         }
-        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N]\n"); return 1; }
+        else { fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N] [--assign FILE [--uncertainty] [--haplotypes] [--truth TRUE]]\n"); return 1; }
     }
     if (mat_f.empty() || reads_f.empty() || ref_f.empty()) {
-        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N]\n");
+        fprintf(stderr, "usage: wepp-epp -i tree.pb -r reads.pb -f ref.fa [-m mask.bed] -d outdir [--device N] [--assign FILE [--resolve RESIDUAL]] [--neighbors FILE [--radius R] [--max-neighbors L]] [--peaks [--top-n T] [--max-peaks P] [--peak-radius Q]] [--clade-idx N] [--assign FILE [--uncertainty] [--haplotypes] [--truth TRUE]]\n");
         return 1;
     }
     if (!resolve_f.empty() && assign_f.empty()) {
         fprintf(stderr, "ERROR: --resolve needs --assign: residual mutations are attributed to the selected haplotypes\n");
+        return 1;
+    }
+    if ((want_uncertainty || want_haplotypes || !truth_f.empty()) && assign_f.empty()) {
+        fprintf(stderr, "ERROR: %s needs --assign: FILE names the selected haplotypes\n", want_uncertainty ? "--uncertainty" : want_haplotypes ? "--haplotypes" : "--truth");
         return 1;
     }
     if (clade_idx >= 0 && assign_f.empty() && !dump) {
@@ -203,6 +274,24 @@ int main(int argc, char** argv) {
         std::vector<double> abundance;
         if (!assign_f.empty() && !read_selection(assign_f, selected, selected_ids, clade_idx >= 0 ? &abundance : nullptr)) return 1;
         if (!neighbors_f.empty() && !read_selection(neighbors_f, pivots, pivot_ids)) return 1;
+        // so are the true nodes
+        std::vector<MAT::Node*> true_nodes;
+        if (!truth_f.empty()) {
+            std::ifstream in(truth_f);
+            if (!in.is_open()) { fprintf(stderr, "ERROR: cannot read %s\n", truth_f.c_str()); return 1; }
+            std::unordered_set<MAT::Node*> seen;
+            std::string line;
+            while (std::getline(in, line)) {
+                if (!line.empty() && line.back() == '\r') line.pop_back();
+                if (line.empty()) continue;
+                MAT::Node* n = T.get_node(line);
+                if (!n) { fprintf(stderr, "ERROR: %s: %s is not a node of the tree\n", truth_f.c_str(), line.c_str()); return 1; }
+                if (!seen.insert(n).second) { fprintf(stderr, "ERROR: %s: %s is listed more than once\n", truth_f.c_str(), line.c_str()); return 1; }
+                true_nodes.push_back(n);
+            }
+            if (true_nodes.empty()) { fprintf(stderr, "ERROR: %s names no node\n", truth_f.c_str()); return 1; }
+        }
+        const std::string ref_name = want_haplotypes ? load_reference_name(ref_f) : std::string();
         // so is the residual list
         std::vector<residual_mutation> residual;
         if (!resolve_f.empty()) residual = load_residual_mutations(resolve_f, reference);
@@ -265,6 +354,35 @@ int main(int argc, char** argv) {
             for (size_t k = 0; k < selected.size(); k++)
                 fprintf(f, "%s,%s\n", selected_ids[k].c_str(), std::to_string(asg.coverage[k]).c_str());   // arena.cpp:681-688
             fclose(f);
+        }
+        if (want_uncertainty) {
+            std::vector<int> max_dist;
+            if (haplotype_uncertainty(selected, mappings, max_dist, device) != 0) return 1;
+            f = fopen((outdir + "/haplotype_uncertainty.csv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            for (size_t k = 0; k < selected.size(); k++) fputs(uncertainty_row(max_dist[k], mappings[selected[k]]).c_str(), f);
+            fclose(f);
+        }
+        if (want_haplotypes) {
+            f = fopen((outdir + "/haplotypes.tsv").c_str(), "w");
+            if (!f) { fprintf(stderr, "ERROR: cannot write into %s\n", outdir.c_str()); return 1; }
+            genotype_lister lister;
+            for (MAT::Node* hap : selected)                                     // hap->id names the first source node (arena.cpp:915)
+                fputs(haplotype_row(hap->identifier, ref_name, reference, lister.get_mutations(mappings[hap].front())).c_str(), f);
+            fclose(f);
+        }
+        if (!true_nodes.empty()) {
+            std::vector<MAT::Node*> predicted;
+            for (MAT::Node* hap : selected) predicted.push_back(mappings[hap].front());
+            std::vector<int> min_dist, nearest;
+            if (truth_distances(true_nodes, predicted, site_read_map(reads, mask), min_dist, nearest, device) != 0) return 1;
+            printf("--- ground truth %zu haps; predicted %zu haps\n", true_nodes.size(), selected.size());
+            double average_dist = 0.0;
+            for (size_t t = 0; t < true_nodes.size(); t++) {
+                average_dist += (double)min_dist[t] / true_nodes.size();       // arena.cpp:296
+                fputs(truth_row(min_dist[t], true_nodes[t]->identifier, selected[(size_t)nearest[t]]->identifier).c_str(), stdout);
+            }
+            printf("average mutation_distance: %0.3f\n", average_dist);
         }
         if (clade_idx >= 0 && !selected.empty()) {
             const bool in_range = clade_idx <= max_clades_idx;
