@@ -431,6 +431,21 @@ hipError_t launch_finalize(const DevMAT& m, const uint32_t* d_read_off, const ui
                            const uint32_t* list, uint32_t n_list, uint32_t nchunks, const int32_t* part_score,
                            const uint32_t* part_rank, const uint32_t* part_cnt, uint32_t* best_bfs_j,
                            int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream);
+// k_scores runs one wave per (read, chunk of the stream).  The chunks of a launch: enough waves to fill the chip
+// (PASS2_TARGET_WAVES over the reads), cut at checkpoints; the list of optimal nodes (emit) takes no chunk shorter than
+// PASS2_MIN_CHUNK_BLOCKS blocks.  launch_scores and launch_best_nodes both launch what this returns, and the
+// `[scores]` / `[best_nodes]` debug lines print it.
+constexpr uint32_t PASS2_TARGET_WAVES = 8192, PASS2_MIN_CHUNK_BLOCKS = 8;
+struct Pass2Chunks { uint32_t nchunks, bpc; };
+inline Pass2Chunks pass2_chunks(uint32_t n_reads, uint32_t NB, uint32_t ncp, uint32_t cp_stride, bool emit) {
+    uint32_t nchunks = (PASS2_TARGET_WAVES + n_reads - 1) / n_reads;
+    if (nchunks < 1) nchunks = 1;
+    const uint32_t longest = NB / PASS2_MIN_CHUNK_BLOCKS < 1 ? 1 : NB / PASS2_MIN_CHUNK_BLOCKS;
+    if (emit && nchunks > longest) nchunks = longest;
+    if (nchunks > ncp) nchunks = ncp;
+    const uint32_t bpc = ((ncp + nchunks - 1) / nchunks) * cp_stride;
+    return Pass2Chunks{(NB + bpc - 1) / bpc, bpc};
+}
 hipError_t launch_scores(const DevMAT& m, const DevStream& full, const uint32_t* d_read_off,
                          const uint32_t* d_read_word, uint32_t n_reads, int32_t* d_out, hipStream_t stream);
 hipError_t launch_best_nodes(const DevMAT& m, const DevStream& st, const uint32_t* d_read_off, const uint32_t* d_read_word,

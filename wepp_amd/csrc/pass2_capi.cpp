@@ -249,8 +249,12 @@ extern "C" int wepp_best_nodes(wepp_mat_t* mat, const uint32_t* read_off, const 
         if (win ? (plan_index(id) >= mat->wstreams.size() || mat->wstreams[plan_index(id)].ncnt != nullptr)
                 : (plan_class(id) != PLAN_SWEEP || plan_index(id) >= mat->streams.size()))
             return set_error(WEPP_EDEVICE, "routing produced an invalid plan id");
-        if (debug_plans) fprintf(stderr, "[best_nodes] %s %u: %u reads\n", win ? "window" : "stream", plan_index(id), count);
-        HIP_TRY(launch_best_nodes(mat->dev, win ? mat->wstreams[plan_index(id)] : mat->streams[plan_index(id)], d.off, d.word,
+        const DevStream& ps = win ? mat->wstreams[plan_index(id)] : mat->streams[plan_index(id)];
+        if (debug_plans) {
+            const Pass2Chunks ch = pass2_chunks(count, ps.NB, ps.ncp, ps.cp_stride, true);
+            fprintf(stderr, "[best_nodes] %s %u: %u reads nchunks=%u bpc=%u\n", win ? "window" : "stream", plan_index(id), count, ch.nchunks, ch.bpc);
+        }
+        HIP_TRY(launch_best_nodes(mat->dev, ps, d.off, d.word,
                                   d.list + info[TI_OFF + id], count, d.best, d.o64, d.cursor, d.nodes, nullptr));
     }
     {

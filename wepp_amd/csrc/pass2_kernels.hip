@@ -4,8 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <algorithm>
-
 #include "device_mat.hpp"
 #include "place_dev.hpp"
 
@@ -298,12 +296,9 @@ __global__ void k_excess(DevMAT m, const uint32_t* __restrict__ read_off, const 
 hipError_t launch_scores(const DevMAT& m, const DevStream& full, const uint32_t* d_read_off,
                          const uint32_t* d_read_word, uint32_t n_reads, int32_t* d_out, hipStream_t stream) {
     // enough waves to fill the chip, cut at checkpoints
-    uint32_t nchunks = std::max<uint32_t>(1, (8192 + n_reads - 1) / n_reads);
-    nchunks = std::min(nchunks, full.ncp);
-    const uint32_t bpc = ((full.ncp + nchunks - 1) / nchunks) * full.cp_stride;
-    nchunks = (full.NB + bpc - 1) / bpc;
-    hipLaunchKernelGGL(k_scores<false>, dim3(n_reads * nchunks), dim3(64), 0, stream, full, m.dfs2bfs, d_read_off,
-                       d_read_word, n_reads, bpc, d_out, BestOut{});
+    const Pass2Chunks ch = pass2_chunks(n_reads, full.NB, full.ncp, full.cp_stride, false);
+    hipLaunchKernelGGL(k_scores<false>, dim3(n_reads * ch.nchunks), dim3(64), 0, stream, full, m.dfs2bfs, d_read_off,
+                       d_read_word, n_reads, ch.bpc, d_out, BestOut{});
     return hipGetLastError();
 }
 
@@ -313,14 +308,10 @@ hipError_t launch_best_nodes(const DevMAT& m, const DevStream& st, const uint32_
                              uint32_t* d_cursor, uint32_t* d_nodes, hipStream_t stream) {
     if (n_list == 0) return hipSuccess;
     // enough waves to fill the chip, cut at checkpoints, no chunk shorter than 8 blocks
-    uint32_t nchunks = std::max<uint32_t>(1, (8192 + n_list - 1) / n_list);
-    nchunks = std::min<uint32_t>(nchunks, std::max<uint32_t>(1, st.NB / 8));
-    nchunks = std::min(nchunks, st.ncp);
-    const uint32_t bpc = ((st.ncp + nchunks - 1) / nchunks) * st.cp_stride;
-    nchunks = (st.NB + bpc - 1) / bpc;
-    if ((uint64_t)n_list * nchunks >= (1ull << 31)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_scores<true>, dim3(n_list * nchunks), dim3(64), 0, stream, st, (const uint32_t*)nullptr, d_read_off,
-                       d_read_word, n_list, bpc, (int32_t*)nullptr, BestOut{list, d_best, d_off, d_cursor, d_nodes, m.rank2bfs});
+    const Pass2Chunks ch = pass2_chunks(n_list, st.NB, st.ncp, st.cp_stride, true);
+    if ((uint64_t)n_list * ch.nchunks >= (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_scores<true>, dim3(n_list * ch.nchunks), dim3(64), 0, stream, st, (const uint32_t*)nullptr, d_read_off,
+                       d_read_word, n_list, ch.bpc, (int32_t*)nullptr, BestOut{list, d_best, d_off, d_cursor, d_nodes, m.rank2bfs});
     return hipGetLastError();
 }
 
