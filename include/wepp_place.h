@@ -724,8 +724,8 @@ int wepp_epp_peaks_last_timing(double *map_ms, double *select_ms, double *hits_m
  * nucleotide masks of the two characters, 15 and is_missing for N) per column whose corrected character differs from
  * the reference character: what load_reads_from_proto (:489-549) makes of the file sam::dump_proto writes.
  * Departures from the reference: among equal reads the one earliest in the input leads the group (order lists the
- * members of a group by ascending input index; the reference's unstable sort leaves both open).  Subsampling
- * (:362-454, std::random_device) is not built: the caller limits the reads.
+ * members of a group by ascending input index; the reference's unstable sort leaves both open).  This call takes
+ * every read it is given; subsampling (:362-454) is wepp_sam_build_subsampled below, with a defined draw.
  * A read_word buffer that is too small (word_capacity < read_off[n_merged]; 0 with read_word = NULL asks for exactly
  * that) follows wepp_epp_map's protocol: EVERY other output is delivered, the words wait in the calling thread and
  * the call returns WEPP_ELIMIT; wepp_sam_fetch_words collects them (and drops them) without recomputing.
@@ -758,6 +758,59 @@ int wepp_sam_fetch_words(uint32_t *read_word, uint64_t capacity);
 /* device time of the calling thread's last wepp_sam_build by phase (HIP events, ms): the pile-up with the keep table;
  * the correction (word counts, their scan, the words); the sort; the merge (flags, scans, the merged batch) */
 int wepp_sam_last_timing(double *pileup_ms, double *correct_ms, double *sort_ms, double *merge_ms);
+
+/* ---- read subsampling in front of sam::build -------------------------------- *
+ * Replaces sam::subsample (src/WEPP/sam2pb.cpp:362-454, SUBSAMPLE_ITERS of config.hpp:6) in front of sam::build: of
+ * n = n_reads > m = max_reads aligned reads, T = trials subsets of m reads are drawn, each is piled up into a table of
+ * its own, and the subset whose allele frequencies have the smallest KL divergence from the whole sample's is kept;
+ * the kept reads are then corrected, sorted and merged as wepp_sam_build does it.
+ * The draw.  f(x) is the splitmix64 finaliser on 64-bit unsigned integers:
+ *     x += 0x9E3779B97F4A7C15;  x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9;  x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ *     return x ^ x >> 31;                                           (f(0) = 0xE220A8397B1DCDAF)
+ * For trial t, h_t = f(seed ^ f(t)) and key(t, r) = f(h_t ^ r) for the read of input index r.  f is a bijection, so
+ * the keys of a trial are distinct; the subset of trial t is the m reads of the smallest keys, that is
+ * key(t, r) <= thr_t with thr_t the m-th smallest key.  A trial's subset depends on seed, t, n and m alone.
+ * The divergence.  F = the raw table of wepp_sam_build step 1 (N not counted, '_' counted), S_i its six columns' sum
+ * at site i, C the number of sites with S_i > 0.  A_t = the same pile-up over the subset of trial t with N counted
+ * too (:419-426), A_i and C_t likewise.  p_ij = F_ij / (S_i * C), q_ij = A_ij / (A_i * C_t) and 0 when A_i = 0,
+ *     D_t = the sum over the cells with F_ij > 0 of p_ij * (ln p_ij - ln max(q_ij, 1e-10))            (:377-392, :429-439)
+ * in IEEE fp64, every operation as written.  The sum is taken in a fixed order without atomics: D_t is a function of
+ * the two tables alone, so trials with equal tables get bit-equal divergences; against a sum of the same terms taken
+ * exactly it is off by rounding only.  The winner is the trial of the smallest D_t, the lowest t among equals.
+ * After the pick the kept reads go through steps 2 and 3 of wepp_sam_build, the keep table of step 2 taken from the
+ * FULL table F (the reference leaves collapsed_frequency_table as it was, :394, :281-314).
+ * Outputs: `out` as for wepp_sam_build with two differences: freq is the full raw table F, and order[s] for
+ * s < n_kept names INPUT reads while group_off and the merged batch range over the kept reads (places 0 .. n_kept).
+ * n_kept = m; kept = the ascending input indices of the kept reads; best_trial; divergence[t] = D_t and
+ * threshold[t] = thr_t for every trial (either may be NULL).  The word-buffer protocol is wepp_sam_build's
+ * (WEPP_ELIMIT, wepp_sam_fetch_words), and wepp_sam_last_timing reports the full pile-up and the stages over the kept
+ * reads.
+ * n_reads <= max_reads: nothing is drawn, the call is wepp_sam_build: the same outputs, n_kept = n_reads, kept the
+ * identity, best_trial = UINT32_MAX, divergence and threshold zeroed.
+ * Departures from the reference: the draw is the seeded hash order above, not std::shuffle of an mt19937 seeded from
+ * std::random_device (which has no defined result); ties go to the lowest trial, where the reference's winner among
+ * equals depends on thread timing.
+ * WEPP_EINVAL, besides those of wepp_sam_build: max_reads == 0, trials == 0, a null sub / sub_out / n_kept /
+ * best_trial / kept.  WEPP_ELIMIT, besides those: trials > 65 536.
+ * On the device the trials' tables (genome_size * 24 bytes each) are worked off in passes of consecutive trials that
+ * hold at most 256 MiB of tables (SUB_PASS_BYTES, wepp_amd/csrc/sam_subsample.hpp; at least 8 trials a pass).
+ * WEPP_SAM_SUBSAMPLE_PASS_BYTES in the environment (diagnostic, read once per call) lowers the bound; the results do
+ * not depend on it. */
+typedef struct { uint64_t seed; uint32_t max_reads; uint32_t trials; } wepp_sam_subsample_params;
+typedef struct {
+    uint32_t *n_kept;       /* [1] */
+    uint32_t *kept;         /* [max_reads] ascending input indices of the kept reads */
+    uint32_t *best_trial;   /* [1]; UINT32_MAX when nothing was drawn */
+    double   *divergence;   /* [trials] or NULL */
+    uint64_t *threshold;    /* [trials] or NULL: thr_t */
+} wepp_sam_subsample_out;
+int wepp_sam_build_subsampled(int device, const uint8_t *reference, uint32_t genome_size, const wepp_sam_reads *reads,
+                              const wepp_sam_params *params, const wepp_sam_subsample_params *sub,
+                              wepp_sam_out *out, wepp_sam_subsample_out *sub_out);
+/* device time of the calling thread's last wepp_sam_build_subsampled by phase (HIP events, ms; zero when nothing was
+ * drawn): the thresholds; the tiles' read lists with the trial pile-ups and divergences; the pick with the compaction
+ * of the kept reads */
+int wepp_sam_subsample_last_timing(double *select_ms, double *trials_ms, double *pick_ms);
 
 /* ---- pairwise distances between genotypes (haplotype uncertainty, truth report) ---- *
  * The primitive behind dump_haplotype_uncertainty (src/WEPP/arena.cpp:494-528) and print_mutation_distance

@@ -26,7 +26,7 @@ done
 SRC=$SCRATCH/wepp_amd/csrc
 FLAGS="-O3 -std=c++17 -fPIC -Wno-unused-parameter ${EXTRA[*]}"
 pids=()
-for f in flatmat gen errors flat_debug flat_io capi place_batch pass2_capi fitch_capi epp_capi epp_host epp_sweep assign_capi resolve_capi neighbors_capi peaks_capi sam_capi clades_capi geno_capi; do
+for f in flatmat gen errors flat_debug flat_io capi place_batch pass2_capi fitch_capi epp_capi epp_host epp_sweep assign_capi resolve_capi neighbors_capi peaks_capi sam_capi sam_subsample_capi clades_capi geno_capi; do
   /opt/rocm/bin/hipcc $FLAGS -c $SRC/$f.cpp -o $OUT/$f.o & pids+=($!)
 done
 for f in $(cd $SRC && ls *.hip | sed 's/\.hip$//'); do

@@ -165,6 +165,15 @@ class SamParamsC(ctypes.Structure):
     _fields_ = [("min_af", ctypes.c_double), ("min_depth", ctypes.c_uint32)]
 
 
+class SamSubsampleParamsC(ctypes.Structure):
+    _fields_ = [("seed", ctypes.c_uint64), ("max_reads", ctypes.c_uint32), ("trials", ctypes.c_uint32)]
+
+
+class SamSubsampleOutC(ctypes.Structure):
+    _fields_ = [("n_kept", ctypes.c_void_p), ("kept", ctypes.c_void_p), ("best_trial", ctypes.c_void_p), ("divergence", ctypes.c_void_p),
+                ("threshold", ctypes.c_void_p)]
+
+
 class SamOutC(ctypes.Structure):
     _fields_ = [("freq", ctypes.c_void_p), ("n_merged", ctypes.c_void_p), ("order", ctypes.c_void_p), ("group_off", ctypes.c_void_p),
                 ("read_off", ctypes.c_void_p), ("read_word", ctypes.c_void_p), ("start", ctypes.c_void_p), ("end", ctypes.c_void_p),
@@ -244,6 +253,9 @@ _SIGS = {
                                       ctypes.POINTER(SamOutC)]),
     "wepp_sam_fetch_words": (ctypes.c_int, [_V, ctypes.c_uint64]),
     "wepp_sam_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 4),
+    "wepp_sam_build_subsampled": (ctypes.c_int, [ctypes.c_int, _V, ctypes.c_uint32, ctypes.POINTER(SamReadsC), ctypes.POINTER(SamParamsC),
+                                                 ctypes.POINTER(SamSubsampleParamsC), ctypes.POINTER(SamOutC), ctypes.POINTER(SamSubsampleOutC)]),
+    "wepp_sam_subsample_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),
     "wepp_geno_diameters": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GenotypesC), _V, ctypes.c_uint32, ctypes.c_uint32, _V, _V]),
     "wepp_geno_nearest": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(GenotypesC), ctypes.c_uint32, _V, ctypes.c_uint32, _V, _V, _V]),
     "wepp_geno_last_timing": (ctypes.c_int, [ctypes.POINTER(ctypes.c_double)] * 3),

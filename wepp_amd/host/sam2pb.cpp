@@ -1,5 +1,6 @@
-// sam2pb.cpp -- sam2PB of sam_reader.hpp: the parse on the host, sam::build on the device (wepp_sam_build), and the
-// message of sam::dump_proto (src/WEPP/sam2pb.cpp:54-151).
+// sam2pb.cpp -- sam2PB of sam_reader.hpp: the parse on the host, sam::build on the device (wepp_sam_build, or
+// wepp_sam_build_subsampled when a seed is given and more reads are mapped than max_reads), and the message of
+// sam::dump_proto (src/WEPP/sam2pb.cpp:54-151) over the reads that were kept.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -47,7 +48,7 @@ sam2pb_stats sam2PB(std::string const& sam_filename, std::string const& referenc
     std::vector<uint64_t> base_off{0};
     std::vector<uint8_t> base;
     stats.mapped = parse_sam(sam_filename, reference.size(), opt.min_phred, [&](sam_aligned_read&& rd) {
-        if ((double)(names.size() + 1) > opt.max_reads)
+        if (!opt.subsample && (double)(names.size() + 1) > opt.max_reads)
             throw mat_error("ERROR: more than --max-reads (" + std::to_string((long long)opt.max_reads) + ") mapped reads: the reference would subsample them at random (sam2pb.cpp:362-454), which has no defined result; nothing was written");
         names.push_back(std::move(rd.raw_name));
         start.push_back((uint32_t)rd.start_idx);
@@ -71,12 +72,29 @@ sam2pb_stats sam2PB(std::string const& sam_filename, std::string const& referenc
     out.n_merged = &M; out.order = order.data(); out.group_off = group_off.data(); out.read_off = read_off.data();
     out.start = m_start.data(); out.end = m_end.data(); out.degree = m_degree.data();
     out.read_word = nullptr; out.word_capacity = 0;          // the words' number is the call's to tell: they are fetched
-    int rc = wepp_sam_build(opt.device, (const uint8_t*)reference.data(), (uint32_t)G, &rd, &par, &out);
+    // more mapped reads than max_reads, and a seed: sam::subsample (:362-454) through the library's defined draw
+    const bool draw = opt.subsample && (double)R > opt.max_reads;
+    std::vector<uint32_t> kept;
+    std::vector<double> divergence;
+    uint32_t n_kept = 0, best_trial = 0;
+    int rc;
+    if (draw) {
+        const wepp_sam_subsample_params sub{opt.subsample_seed, opt.max_reads < 1 ? 0u : (uint32_t)opt.max_reads, opt.subsample_trials};
+        kept.resize(std::max<uint32_t>(sub.max_reads, 1));
+        divergence.resize(std::max<uint32_t>(sub.trials, 1));
+        wepp_sam_subsample_out so{&n_kept, kept.data(), &best_trial, divergence.data(), nullptr};
+        rc = wepp_sam_build_subsampled(opt.device, (const uint8_t*)reference.data(), (uint32_t)G, &rd, &par, &sub, &out, &so);
+    } else {
+        rc = wepp_sam_build(opt.device, (const uint8_t*)reference.data(), (uint32_t)G, &rd, &par, &out);
+    }
     if (rc == WEPP_ELIMIT && M && read_off[M] > 0) {
         words.resize(read_off[M]);
         rc = wepp_sam_fetch_words(words.data(), words.size());
     }
-    if (rc != WEPP_OK) throw mat_error(std::string("wepp_sam_build: ") + wepp_last_error());
+    if (rc != WEPP_OK) throw mat_error(std::string(draw ? "wepp_sam_build_subsampled: " : "wepp_sam_build: ") + wepp_last_error());
+    if (draw) {
+        stats.drawn = true; stats.kept = n_kept; stats.best_trial = best_trial; stats.divergence = divergence[best_trial];
+    }
     stats.device_ms = ms_since(t0);
     stats.merged = M;
 
@@ -99,5 +117,13 @@ sam2pb_stats sam2PB(std::string const& sam_filename, std::string const& referenc
     }
     dump_reads_proto(records, reverse_merge, pb_filename);
     if (!opt.dump_dir.empty()) dump_frequency_table(freq, G, opt.dump_dir + "/frequency_table.tsv");
+    if (!opt.dump_dir.empty() && draw) {
+        const std::string name = opt.dump_dir + "/subsample_trials.tsv";
+        FILE* f = fopen(name.c_str(), "w");
+        if (!f) throw mat_error("ERROR: Could not write " + name);
+        fprintf(f, "trial\tdivergence\tchosen\n");
+        for (uint32_t t = 0; t < opt.subsample_trials; t++) fprintf(f, "%u\t%.17g\t%d\n", t, divergence[t], t == best_trial ? 1 : 0);
+        fclose(f);
+    }
     return stats;
 }

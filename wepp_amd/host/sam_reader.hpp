@@ -8,8 +8,11 @@
 //     TBB range the line happens to lie in;
 //   - among equal reads the one earliest in the file leads the merged read and names it, and reverse_columns lists the
 //     members in file order; the reference's unstable sort leaves both open;
-//   - subsampling (:362-454) draws from std::random_device and has no defined result: more mapped reads than max_reads
-//     is an error and nothing is written;
+//   - subsampling (:362-454) draws from std::random_device and has no defined result.  With a seed
+//     (sam2pb_options::subsample) more mapped reads than max_reads are subsampled by wepp_sam_build_subsampled: the
+//     draw is a seeded hash order instead of std::shuffle of a random_device-seeded mt19937, and among trials of equal
+//     divergence the lowest wins (the reference's winner among equals depends on thread timing).  Without a seed more
+//     mapped reads than max_reads is an error and nothing is written;
 //   - inputs on which the reference reads outside its strings or tables are errors that name the line: fewer than 11
 //     fields, a quality of `*` or shorter than the query, a CIGAR that consumes more bases than the query holds, an
 //     aligned read that starts before position 1 or ends beyond the reference, a CIGAR without an aligned column;
@@ -18,6 +21,7 @@
 // does not match the reference's \d+[A-Za-z] and is passed over.
 #pragma once
 #include <cstddef>
+#include <cstdint>
 #include <functional>
 #include <map>
 #include <string>
@@ -43,8 +47,17 @@ struct sam2pb_options {                            // dataset::min_af / min_dept
     int min_phred = 20;
     double max_reads = 1e9;
     int device = 0;
-    std::string dump_dir;                          // non-empty: <dump_dir>/frequency_table.tsv in the layout of dump_sub_table (:30-52)
+    std::string dump_dir;                          // non-empty: <dump_dir>/frequency_table.tsv in the layout of dump_sub_table (:30-52),
+                                                   // and, when reads were drawn, <dump_dir>/subsample_trials.tsv: trial, divergence (%.17g), chosen
+    bool subsample = false;                        // more mapped reads than max_reads: draw (true) or fail (false)
+    uint64_t subsample_seed = 0;
+    uint32_t subsample_trials = 1000;              // SUBSAMPLE_ITERS (config.hpp:6)
 };
-struct sam2pb_stats { size_t mapped = 0, merged = 0; double parse_ms = 0, device_ms = 0; };
+struct sam2pb_stats {
+    size_t mapped = 0, merged = 0;
+    double parse_ms = 0, device_ms = 0;
+    bool drawn = false;                            // reads were subsampled: kept of mapped, the winning trial and its divergence
+    size_t kept = 0; uint32_t best_trial = 0; double divergence = 0;
+};
 // sam2PB (:54-104): SAM + reference -> the reads .pb[.gz] of sam::dump_proto (:111-151)
 sam2pb_stats sam2PB(std::string const& sam_filename, std::string const& reference, std::string const& pb_filename, sam2pb_options const& opt);
