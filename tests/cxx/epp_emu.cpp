@@ -20,10 +20,7 @@ extern "C" wepp_mat* emu_mat_create(const uint32_t* node_woff, const uint32_t* w
     return m;
 }
 
-extern "C" void emu_mat_destroy(wepp_mat* m) {
-    for (void* p : m->allocs) (void)hipFree(p);
-    delete m;
-}
+extern "C" void emu_mat_destroy(wepp_mat* m) { delete m; }
 
 // 0, or 1 + the index of the first block of the handle's cache whose bytes past the most ever asked of it, or whose
 // guard behind it, are no longer the fill of the emulated hipMalloc

@@ -3,7 +3,7 @@
 // Kernels are compiled as plain C++ and run with ONE HOST THREAD PER LANE, in lock step at every cross-lane operation
 // (__ballot, __shfl_xor: a barrier per wave; __syncthreads: a barrier per workgroup), one workgroup after the other;
 // atomics are the host's.  The runtime is the host's too: device memory is malloc'ed memory, a copy is a memcpy done at
-// once, streams and events do nothing.  So the host sides of the entry points compile unchanged against it.  It checks
+// once, streams and events are tokens that do nothing.  So the host sides of the entry points compile unchanged against it.  It checks
 // logic, indexing, buffer sizes and launch order without a GPU; it says nothing about speed, occupancy, the memory
 // model of the device or asynchrony between streams.
 #include <pthread.h>
@@ -29,7 +29,13 @@ inline uint2 make_uint2(uint32_t a, uint32_t b) { return uint2{a, b}; }
 typedef int hipError_t; typedef void* hipStream_t; typedef void* hipEvent_t;
 constexpr int hipSuccess = 0, hipErrorOutOfMemory = 2;
 enum hipMemcpyKind { hipMemcpyHostToDevice, hipMemcpyDeviceToHost, hipMemcpyDeviceToDevice };
-constexpr unsigned hipHostMallocPortable = 1, hipEventDisableTiming = 2;
+constexpr unsigned hipHostMallocDefault = 0, hipHostMallocPortable = 1, hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000;
+constexpr unsigned hipEventDefault = 0, hipEventDisableTiming = 2, hipStreamNonBlocking = 1;
+// what is alive: device blocks, host blocks, streams, events (tests/cxx/handle_lifetime_main.cpp: all zero once a
+// handle is gone).  emu_malloc_budget: the device allocations that still succeed (negative: all of them).
+struct EmuLive { long dev = 0, host = 0, streams = 0, events = 0; };
+inline EmuLive g_emu_live;
+inline long g_emu_malloc_budget = -1;
 inline hipError_t hipGetLastError() { return 0; }
 inline const char* hipGetErrorString(hipError_t e) { return e ? "emulated HIP error" : "no error"; }
 inline hipError_t hipSetDevice(int) { return 0; }
@@ -41,23 +47,36 @@ inline hipError_t hipStreamSynchronize(hipStream_t) { return 0; }
 constexpr uint32_t EMU_FILL = 0xDEADBEEFu;
 constexpr size_t EMU_GUARD_BYTES = 64;
 inline hipError_t hipMalloc(void** p, size_t bytes) {
+    if (g_emu_malloc_budget == 0) return hipErrorOutOfMemory;
     const size_t words = (bytes + EMU_GUARD_BYTES + 3) / 4;
     uint32_t* w = (uint32_t*)malloc(words * 4);
     if (!w) return hipErrorOutOfMemory;
+    if (g_emu_malloc_budget > 0) g_emu_malloc_budget--;
+    g_emu_live.dev++;
     std::fill(w, w + words, EMU_FILL);
     *p = w;
     return 0;
 }
 template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { return hipMalloc((void**)p, bytes); }
-inline hipError_t hipFree(void* p) { free(p); return 0; }
-inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned = 0) { return (*p = malloc(bytes)) ? 0 : hipErrorOutOfMemory; }
-inline hipError_t hipHostFree(void* p) { free(p); return 0; }
+inline hipError_t hipFree(void* p) { if (p) g_emu_live.dev--; free(p); return 0; }
+inline hipError_t hipHostMalloc(void** p, size_t bytes, unsigned = 0) {
+    if (!(*p = malloc(bytes))) return hipErrorOutOfMemory;
+    g_emu_live.host++;
+    return 0;
+}
+inline hipError_t hipHostFree(void* p) { if (p) g_emu_live.host--; free(p); return 0; }
+inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) { *dev = host; return 0; }
+inline hipError_t hipMemset(void* dst, int v, size_t bytes) { if (bytes) memset(dst, v, bytes); return 0; }
 inline hipError_t hipMemcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind) { if (bytes) memcpy(dst, src, bytes); return 0; }
 inline hipError_t hipMemcpyAsync(void* dst, const void* src, size_t bytes, hipMemcpyKind k, hipStream_t) { return hipMemcpy(dst, src, bytes, k); }
 inline hipError_t hipMemsetAsync(void* dst, int v, size_t bytes, hipStream_t) { if (bytes) memset(dst, v, bytes); return 0; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = nullptr; return 0; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = nullptr; return 0; }
-inline hipError_t hipEventDestroy(hipEvent_t) { return 0; }
+// streams and events are small heap tokens, so that a leak or a second destroy shows under AddressSanitizer; nothing
+// looks into them (the null stream is a stream too)
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = malloc(1); g_emu_live.streams++; return 0; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { g_emu_live.streams--; free(s); return 0; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = malloc(1); g_emu_live.events++; return 0; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, hipEventDefault); }
+inline hipError_t hipEventDestroy(hipEvent_t e) { g_emu_live.events--; free(e); return 0; }
 inline hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return 0; }
 inline hipError_t hipEventSynchronize(hipEvent_t) { return 0; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return 0; }

@@ -16,86 +16,207 @@
 #include <thread>
 #include <vector>
 
-#include "handle.hpp"
+#include "handle_setup.hpp"
 #include "info_wait.hpp"
-
-namespace {
-
-// handles alive in this process: a handle's host workers are its share of the cores the process may use
-std::atomic<uint32_t> g_handles_alive{0};
-
-void release(wepp_mat* h) {
-    if (!h) return;
-    g_handles_alive.fetch_sub(1, std::memory_order_relaxed);
-    (void)hipSetDevice(h->device);
-    for (void* p : h->allocs) (void)hipFree(p);
-    for (PlaceLane& L : h->lane) {
-        if (L.ws) (void)hipFree(L.ws);
-        if (L.part) (void)hipFree(L.part);
-        if (L.d_info) (void)hipFree(L.d_info);
-        if (L.h_info) (void)hipHostFree(L.h_info);
-        for (uint32_t i = 0; i < MAX_STREAMS; i++) {
-            if (L.side[i]) (void)hipStreamDestroy(L.side[i]);
-            if (L.join_ev[i]) (void)hipEventDestroy(L.join_ev[i]);
-        }
-        if (L.fork_ev) (void)hipEventDestroy(L.fork_ev);
-        if (L.route_ev) (void)hipEventDestroy(L.route_ev);
-        if (L.info_ev) (void)hipEventDestroy(L.info_ev);
-        if (L.d_seed_heavy) (void)hipFree(L.d_seed_heavy);
-    }
-    if (h->io_in) (void)hipFree(h->io_in);
-    if (h->io_out) (void)hipFree(h->io_out);
-    if (h->pin) (void)hipHostFree(h->pin);
-    if (h->d_work) (void)hipFree(h->d_work);
-    for (uint32_t i = 0; i < wepp_mat::kRing; i++) {
-        if (h->ev0[i]) (void)hipEventDestroy(h->ev0[i]);
-        if (h->ev1[i]) (void)hipEventDestroy(h->ev1[i]);
-    }
-    for (uint32_t i = 0; i < wepp_mat::kPipeMax; i++) {
-        if (h->pipe_up[i]) (void)hipEventDestroy(h->pipe_up[i]);
-        if (h->pipe_done[i]) (void)hipEventDestroy(h->pipe_done[i]);
-    }
-    for (uint32_t i = 0; i < 4 * wepp_mat::kPipeMax; i++)
-        if (h->pipe_out[i]) (void)hipEventDestroy(h->pipe_out[i]);
-    for (hipStream_t st : h->pipe_h2d) if (st) (void)hipStreamDestroy(st);
-    for (hipStream_t st : h->pipe_d2h) if (st) (void)hipStreamDestroy(st);
-    for (hipStream_t st : h->pipe_compute)
-        if (st) (void)hipStreamDestroy(st);
-    if (h->pin_out) (void)hipHostFree(h->pin_out);
-    if (h->d_plan_of) (void)hipFree(h->d_plan_of);
-    if (h->d_wsid_of) (void)hipFree(h->d_wsid_of);
-    delete h;
-}
-
-}  // namespace
 
 namespace wepp {
 
-uint32_t handles_alive() { return g_handles_alive.load(std::memory_order_relaxed); }
-
 size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// A grow-only buffer of a handle, in device or in pinned host memory: kept while it holds `need` bytes; else freed --
-// behind a device-wide synchronisation: work in flight may still use it, hipFree waits for the device anyway, and a
-// buffer regrows only while its handle warms up -- and allocated again with need / slack bytes to spare.
-int grow_only(void*& p, size_t& have, size_t need, size_t slack, bool pinned, const char* what) {
-    if (need <= have) return WEPP_OK;
-    if (p) {
-        HIP_TRY(hipDeviceSynchronize());
-        (void)(pinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        have = 0;
-    }
-    const size_t bytes = need + need / slack;
-    const hipError_t e = pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
-    if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string(pinned ? "hipHostMalloc " : "hipMalloc ") + what + ": " + hipGetErrorString(e));
-    have = bytes;
-    return WEPP_OK;
-}
 
 }  // namespace wepp
 
 namespace {
+// The sweep loads two events per lane from every block start and the summaries of the next three blocks without
+// looking at the stream's end: a stream's event words, bounds and block summaries are appended with padding behind
+// the last event / block.
+void append_padded(const Stream& st, std::vector<uint32_t>& evw, std::vector<uint8_t>& evl, std::vector<BlkSum>& sums) {
+    evw.insert(evw.end(), st.ev_word.begin(), st.ev_word.end());
+    evw.resize(evw.size() + EV_TAIL_PAD, W_PAD);
+    evl.insert(evl.end(), st.ev_lb.begin(), st.ev_lb.end());
+    evl.resize(evl.size() + EV_TAIL_PAD, 255);
+    sums.insert(sums.end(), st.blk_sum.begin(), st.blk_sum.end());
+    sums.resize(sums.size() + SUM_TAIL_PAD, st.blk_sum.empty() ? BlkSum{} : st.blk_sum.back());
+}
+
+int up_stream(wepp_mat* h, const Stream& st, uint32_t tier, DevStream& ds) {
+    ds = DevStream{};
+    ds.n = st.n;
+    ds.NB = st.NB;
+    ds.cp_stride = st.cp_stride;
+    ds.ncp = (uint32_t)st.cp_off.size() - 1;
+    ds.eager = 1u;                 // (crown and window streams; the whole-tree stream clears it)
+    ds.tier = tier;
+    ds.e_pad = (uint32_t)st.E;
+    WEPP_TRY(upload(h, st.nkey, &ds.nkey));
+    WEPP_TRY(upload(h, st.nstat, &ds.nstat));
+    WEPP_TRY(upload(h, st.blk_node0, &ds.blk_node0));
+    WEPP_TRY(upload(h, st.blk_eoff, &ds.blk_eoff));
+    WEPP_TRY(upload(h, st.ev_meta, &ds.ev_meta));
+    WEPP_TRY(upload(h, st.cp_off, &ds.cp_off));
+    WEPP_TRY(upload(h, st.cp_word, &ds.cp_word));
+    if (!st.ncnt.empty()) WEPP_TRY(upload(h, st.ncnt, &ds.ncnt));
+    std::vector<uint32_t> evw;
+    std::vector<uint8_t> evl;
+    std::vector<BlkSum> sums;
+    append_padded(st, evw, evl, sums);
+    WEPP_TRY(upload(h, evw, &ds.ev_word));
+    WEPP_TRY(upload(h, evl, &ds.ev_lb));
+    return upload(h, sums, &ds.blk_sum);
+}
+
+// ---- the WALK ARENA: the walk structures (position index, range-query tables) of every stream -- the window crowns
+// first, then the tree-wide streams -- slice by slice in ONE allocation per array (device_mat.hpp: WcInfo = the
+// offsets of a stream's slices; entry indices are absolute in the arena).  Which stream a read walks is a per-READ
+// value (k_route: wsid), so one launch of k_walk serves the reads of all streams, sized without a look at the routing
+// counters. ----
+struct ArenaOff { size_t n = 0, ent = 0, head = 0, nest = 0, sp = 0, dst = 0; };   // elements in front of a slice, array by array (nrec, rq_pre and rq_suf share n)
+struct ArenaSlice {
+    const Stream* st;
+    size_t info;                   // its WcInfo
+    DevWalk* view;                 // a tree-wide stream's own DevWalk (null: a window crown)
+};
+
+WcInfo slice_info(const FlatMAT& f, const Stream& st, const ArenaOff& o) {
+    WcInfo wi{};
+    wi.n = st.n;
+    wi.rq_blocks = st.rq_blocks;
+    wi.last_ent = (uint32_t)(o.ent + st.ix_ent.size() - 1);
+    wi.has_pre = st.ix_pre.empty() ? 0u : st.ix_pre[0];
+    wi.node_off = (uint32_t)o.n;
+    wi.head_off = (uint32_t)o.head;
+    wi.nest_off = (uint32_t)o.nest;
+    wi.dst_off = (uint32_t)o.dst;
+    wi.sp_off = o.sp;
+    wi.tau = st.tau;
+    wi.whole = st.whole;
+    wi.whole_bfs = f.rank2bfs[st.whole.rank < f.N ? st.whole.rank : 0u];
+    return wi;
+}
+
+template <typename T>
+hipError_t copy_slice(T* dst, const std::vector<T>& v) {
+    return v.empty() ? hipSuccess : hipMemcpy(dst, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+int build_walk_arena(const FlatMAT& f, wepp_mat* h) {
+    DevMAT& d = h->dev;
+    const size_t n_wc = f.wcrowns.size() * WC_MAX;
+    std::vector<ArenaSlice> slices;
+    for (size_t w = 0; w < f.wcrowns.size(); w++)
+        for (size_t i = 0; i < f.wcrowns[w].size(); i++) slices.push_back(ArenaSlice{&f.wcrowns[w][i], w * WC_MAX + i, nullptr});
+    for (size_t i = 0; i < f.streams.size(); i++) slices.push_back(ArenaSlice{&f.streams[i], n_wc + i, &h->walks[i]});
+    ArenaOff tot;
+    for (const ArenaSlice& s : slices) {
+        tot.n += s.st->n; tot.ent += s.st->ix_ent.size(); tot.head += s.st->ix_head.size(); tot.sp += s.st->sp.size(); tot.dst += s.st->rq_dst.size();
+    }
+    if (tot.ent >= 0xFFFFFFF0ull || tot.n >= 0xFFFFFFF0ull || tot.head >= 0xFFFFFFF0ull || tot.dst >= 0xFFFFFFF0ull)
+        return set_error(WEPP_ELIMIT, "the walk structures exceed 2^32 index entries");
+    IxHead* g_head; IxEnt* g_ent; uint8_t *g_nest, *g_sp; NodeRec* g_nrec; SegNode *g_pre, *g_suf, *g_dst;
+    uint32_t* g_rtpos;                         // k_route's word per head slot, derived from g_head and g_nest slice by slice (route_pos.hpp)
+    WEPP_TRY(dev_alloc(h, tot.head, &g_head));
+    WEPP_TRY(dev_alloc(h, tot.ent, &g_ent));
+    WEPP_TRY(dev_alloc(h, tot.head, &g_nest));
+    WEPP_TRY(dev_alloc(h, tot.sp, &g_sp));
+    WEPP_TRY(dev_alloc(h, tot.n, &g_nrec));
+    WEPP_TRY(dev_alloc(h, tot.n, &g_pre));
+    WEPP_TRY(dev_alloc(h, tot.n, &g_suf));
+    WEPP_TRY(dev_alloc(h, tot.dst, &g_dst));
+    WEPP_TRY(dev_alloc(h, tot.head, &g_rtpos));
+    d.rt_pos = g_rtpos;
+    // every slice's arrays are copied from the image into place, its entry indices rebased by a kernel
+    std::vector<WcInfo> info(n_wc + f.streams.size());
+    ArenaOff o;
+    for (const ArenaSlice& s : slices) {
+        const Stream& st = *s.st;
+        // (the window crowns' nesting bytes are packed, one fewer than heads per crown; a tree-wide stream's sit at its head offset)
+        if (s.view) o.nest = o.head;
+        const WcInfo& wi = info[s.info] = slice_info(f, st, o);
+        HIP_TRY(copy_slice(g_head + o.head, st.ix_head));
+        HIP_TRY(copy_slice(g_ent + o.ent, st.ix_ent));
+        HIP_TRY(copy_slice(g_nest + o.nest, st.ix_nest));
+        HIP_TRY(copy_slice(g_sp + o.sp, st.sp));
+        HIP_TRY(copy_slice(g_nrec + o.n, st.nrec));
+        HIP_TRY(copy_slice(g_pre + o.n, st.rq_pre));
+        HIP_TRY(copy_slice(g_suf + o.n, st.rq_suf));
+        HIP_TRY(copy_slice(g_dst + o.dst, st.rq_dst));
+        if (o.ent) HIP_TRY(launch_rebase_index(g_head + o.head, (uint32_t)st.ix_head.size(), g_ent + o.ent, (uint32_t)st.ix_ent.size(), (uint32_t)o.ent, nullptr));
+        HIP_TRY(launch_route_pos(g_head + o.head, g_nest + o.nest, (uint32_t)st.ix_head.size(), g_rtpos + o.head, nullptr));
+        if (s.view) {
+            // the stream's own view (plan-wise users: k_route, the chunked walks): entry indices are absolute, so the
+            // entries are addressed from the arena's base; positions and nodes are the stream's own
+            DevWalk& dw = *s.view;
+            dw.n = st.n; dw.rq_blocks = st.rq_blocks; dw.last_ent = wi.last_ent; dw.has_pre = wi.has_pre; dw.whole = st.whole;
+            dw.ix_head = g_head + o.head; dw.ix_ent = g_ent; dw.ix_nest = g_nest + o.nest; dw.nrec = g_nrec + o.n;
+            dw.rq_pre = g_pre + o.n; dw.rq_suf = g_suf + o.n; dw.rq_dst = g_dst + o.dst; dw.sp = g_sp + o.sp;
+        } else {
+            h->wc_nodes += st.n;
+            h->wc_count++;
+        }
+        o.n += st.n; o.ent += st.ix_ent.size(); o.head += st.ix_head.size(); o.nest += st.ix_nest.size(); o.sp += st.sp.size(); o.dst += st.rq_dst.size();
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    d.tw_base = (uint32_t)n_wc;
+    // ... and the window crowns' sweep streams, for the reads that cannot walk (k_sweep_arena): the same kind of arena;
+    // every stream keeps its own tail padding
+    {
+        std::vector<int64_t> s_nkey;
+        std::vector<uint32_t> s_nstat, s_node0, s_eoff, s_evw, s_cpo, s_cpw;
+        std::vector<uint8_t> s_meta, s_lb;
+        std::vector<BlkSum> s_sum;
+        struct Off { size_t nkey, node0, eoff, sum, ev, cpo, cpw; };
+        std::vector<Off> offs;
+        for (const auto& wc : f.wcrowns)
+            for (const Stream& st : wc) {
+                offs.push_back(Off{s_nkey.size(), s_node0.size(), s_eoff.size(), s_sum.size(), s_evw.size(), s_cpo.size(), s_cpw.size()});
+                s_nkey.insert(s_nkey.end(), st.nkey.begin(), st.nkey.end());
+                s_nstat.insert(s_nstat.end(), st.nstat.begin(), st.nstat.end());
+                s_node0.insert(s_node0.end(), st.blk_node0.begin(), st.blk_node0.end());
+                s_eoff.insert(s_eoff.end(), st.blk_eoff.begin(), st.blk_eoff.end());
+                append_padded(st, s_evw, s_lb, s_sum);
+                s_meta.insert(s_meta.end(), st.ev_meta.begin(), st.ev_meta.end());
+                s_meta.resize(s_meta.size() + EV_TAIL_PAD, 0);
+                s_cpo.insert(s_cpo.end(), st.cp_off.begin(), st.cp_off.end());
+                s_cpw.insert(s_cpw.end(), st.cp_word.begin(), st.cp_word.end());
+            }
+        const int64_t* d_nkey; const uint32_t *d_nstat, *d_node0, *d_eoff, *d_evw, *d_cpo, *d_cpw;
+        const uint8_t *d_meta, *d_lb; const BlkSum* d_sum;
+        WEPP_TRY(upload(h, s_nkey, &d_nkey));
+        WEPP_TRY(upload(h, s_nstat, &d_nstat));
+        WEPP_TRY(upload(h, s_node0, &d_node0));
+        WEPP_TRY(upload(h, s_eoff, &d_eoff));
+        WEPP_TRY(upload(h, s_sum, &d_sum));
+        WEPP_TRY(upload(h, s_evw, &d_evw));
+        WEPP_TRY(upload(h, s_meta, &d_meta));
+        WEPP_TRY(upload(h, s_lb, &d_lb));
+        WEPP_TRY(upload(h, s_cpo, &d_cpo));
+        WEPP_TRY(upload(h, s_cpw, &d_cpw));
+        std::vector<DevStream> ws(n_wc, DevStream{});
+        size_t k = 0;
+        for (size_t w = 0; w < f.wcrowns.size(); w++)
+            for (size_t i = 0; i < f.wcrowns[w].size(); i++, k++) {
+                const Stream& st = f.wcrowns[w][i];
+                DevStream& ds = ws[w * WC_MAX + i];
+                ds.n = st.n; ds.NB = st.NB; ds.cp_stride = st.cp_stride; ds.ncp = (uint32_t)st.cp_off.size() - 1;
+                ds.eager = 1u; ds.tier = WC_SLOT; ds.e_pad = (uint32_t)st.E;
+                ds.nkey = d_nkey + offs[k].nkey; ds.nstat = d_nstat + offs[k].nkey;
+                ds.blk_node0 = d_node0 + offs[k].node0; ds.blk_eoff = d_eoff + offs[k].eoff; ds.blk_sum = d_sum + offs[k].sum;
+                ds.ev_word = d_evw + offs[k].ev; ds.ev_meta = d_meta + offs[k].ev; ds.ev_lb = d_lb + offs[k].ev;
+                ds.cp_off = d_cpo + offs[k].cpo; ds.cp_word = d_cpw + offs[k].cpw;
+            }
+        WEPP_TRY(upload(h, ws, &d.wc_streams));
+    }
+    WEPP_TRY(upload(h, info, &d.wc_info));
+    d.wc_windows = (uint32_t)f.wcrowns.size();
+    h->stats.n_window_crowns = h->wc_count;
+    h->stats.window_crown_nodes = h->wc_nodes;
+    h->walks.resize(MAX_STREAMS, DevWalk{});
+    DevWalk arena{};                           // (n = 0: never a stream of its own)
+    arena.ix_head = g_head; arena.ix_ent = g_ent; arena.ix_nest = g_nest; arena.sp = g_sp;
+    arena.nrec = g_nrec; arena.rq_pre = g_pre; arena.rq_suf = g_suf; arena.rq_dst = g_dst;
+    h->walks[WC_SLOT] = arena;
+    return WEPP_OK;
+}
+
 // the device half of wepp_mat_create: the flat image `f` (flatmat.hpp) copied into HBM of `device`, plus the handle's
 // streams, events and counters.  The image is only read: one image serves any number of devices / handles.
 int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
@@ -107,11 +228,10 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     if (device < 0 || device >= ndev) return set_error(WEPP_EINVAL, "device index out of range");
     HIP_TRY(hipSetDevice(device));
 
-    wepp_mat* h = new (std::nothrow) wepp_mat();
+    // (every error return below frees the handle with what it holds by then; the successful return lets go of it)
+    std::unique_ptr<wepp_mat> owner(new (std::nothrow) wepp_mat());
+    wepp_mat* const h = owner.get();
     if (!h) return set_error(WEPP_ENOMEM, "out of host memory");
-    g_handles_alive.fetch_add(1, std::memory_order_relaxed);
-    // (every error return below releases the handle with what it holds by then; the successful return lets go of it)
-    std::unique_ptr<wepp_mat, void (*)(wepp_mat*)> owner(h, release);
     h->device = device;
     h->bfs2id = f.bfs2id;
     h->dfs2id = f.dfs2id;
@@ -135,46 +255,25 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     d.root_base = f.root_base;
     h->tun = PlaceTunables::from_env();
     d.walk_eager_nodes = h->tun.walk_eager_nodes;
-    int rc;
-#define UP(dst, vec) if ((rc = upload(h, vec, &dst)) != WEPP_OK) return rc;
-    // (inside up_stream too a failure returns the code: `owner` releases the handle wherever upload_flat returns)
-    UP(d.node_woff, f.node_woff) UP(d.words, f.words) UP(d.nstat, f.nstat) UP(d.rank2dfs, f.rank2dfs)
-    UP(d.dfs2bfs, f.dfs2bfs) UP(d.rank2bfs, f.rank2bfs)
+    WEPP_TRY(upload(h, f.node_woff, &d.node_woff));
+    WEPP_TRY(upload(h, f.words, &d.words));
+    WEPP_TRY(upload(h, f.nstat, &d.nstat));
+    WEPP_TRY(upload(h, f.rank2dfs, &d.rank2dfs));
+    WEPP_TRY(upload(h, f.dfs2bfs, &d.dfs2bfs));
+    WEPP_TRY(upload(h, f.rank2bfs, &d.rank2bfs));
     {
         std::vector<uint32_t> bfs2dfs(f.N);
         for (uint32_t k = 0; k < f.N; k++) bfs2dfs[f.dfs2bfs[k]] = k;
-        UP(d.bfs2dfs, bfs2dfs)
+        WEPP_TRY(upload(h, bfs2dfs, &d.bfs2dfs));
     }
-    UP(d.parent_dfs, f.parent_dfs)
-    UP(d.maxnest, f.maxnest)
-    UP(h->epp_word, f.epp_word) UP(h->epp_node, f.epp_node)
+    WEPP_TRY(upload(h, f.parent_dfs, &d.parent_dfs));
+    WEPP_TRY(upload(h, f.maxnest, &d.maxnest));
+    WEPP_TRY(upload(h, f.epp_word, &h->epp_word));
+    WEPP_TRY(upload(h, f.epp_node, &h->epp_node));
     h->epp_events = f.epp_word.size();
-    auto up_stream = [&](const Stream& st, uint32_t tier, DevStream& ds) -> int {
-        ds = DevStream{};
-        ds.n = st.n;
-        ds.NB = st.NB;
-        ds.cp_stride = st.cp_stride;
-        ds.ncp = (uint32_t)st.cp_off.size() - 1;
-        ds.eager = 1u;                 // (crown and window streams; the whole-tree stream clears it below)
-        ds.tier = tier;
-        ds.e_pad = (uint32_t)st.E;
-        UP(ds.nkey, st.nkey) UP(ds.nstat, st.nstat) UP(ds.blk_node0, st.blk_node0) UP(ds.blk_eoff, st.blk_eoff)
-        UP(ds.ev_meta, st.ev_meta) UP(ds.cp_off, st.cp_off) UP(ds.cp_word, st.cp_word)
-        if (!st.ncnt.empty()) UP(ds.ncnt, st.ncnt)
-        // the sweep loads two events per lane from every block start and the summaries of the next
-        // three blocks without looking at the stream's end: padding behind the last event / block
-        std::vector<uint32_t> evw(st.ev_word);
-        evw.resize(evw.size() + EV_TAIL_PAD, W_PAD);
-        std::vector<uint8_t> evl(st.ev_lb);
-        evl.resize(evl.size() + EV_TAIL_PAD, 255);
-        std::vector<BlkSum> sums(st.blk_sum);
-        sums.resize(sums.size() + SUM_TAIL_PAD, sums.empty() ? BlkSum{} : sums.back());
-        UP(ds.ev_word, evw) UP(ds.ev_lb, evl) UP(ds.blk_sum, sums)
-        return WEPP_OK;
-    };
     for (size_t i = 0; i < f.wstreams.size(); i++) {
         DevStream ds;
-        if ((rc = up_stream(f.wstreams[i], (uint32_t)(f.streams.size() - 1), ds)) != WEPP_OK) return rc;
+        WEPP_TRY(up_stream(h, f.wstreams[i], (uint32_t)(f.streams.size() - 1), ds));
         h->wstreams.push_back(ds);
         h->wstream_bytes.push_back(f.wstreams[i].stream_bytes());
         if (i < MAX_WINDOWS) d.win_n[i] = f.wstreams[i].ncnt.empty() ? f.wstreams[i].n : 0xFFFFFFFFu;   // (pseudo-nodes: the whole tree)
@@ -183,193 +282,26 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
         h->stats.window_stream_nodes += f.wstreams[i].n;
     }
     d.n_windows = (uint32_t)f.wstreams.size();
-    if (!h->wstreams.empty()) UP(h->d_wstreams, h->wstreams)
+    if (!h->wstreams.empty()) WEPP_TRY(upload(h, h->wstreams, &h->d_wstreams));
     for (size_t i = 0; i < f.streams.size(); i++) {
         const Stream& st = f.streams[i];
         DevStream ds;
-        if ((rc = up_stream(st, (uint32_t)i, ds)) != WEPP_OK) return rc;
+        WEPP_TRY(up_stream(h, st, (uint32_t)i, ds));
         if (i + 1 == f.streams.size()) ds.eager = 0u;      // the whole tree prunes with the block minimum
         h->streams.push_back(ds);
         h->stream_bytes.push_back(st.stream_bytes());
-        h->walks.push_back(DevWalk{});      // (a view into the walk arena, filled in below)
+        h->walks.push_back(DevWalk{});      // (a view into the walk arena, filled in by build_walk_arena)
         d.tau[i] = st.tau;
         h->stats.stream_tau[i] = st.tau;
         h->stats.stream_nodes[i] = st.n;
         h->stats.stream_bytes_of[i] = st.stream_bytes();
     }
-    // ---- the WALK ARENA: the walk structures (position index, range-query tables) of every stream -- the window crowns
-    // first, then the tree-wide streams -- concatenated array by array into ONE allocation per array (device_mat.hpp:
-    // WcInfo = the offsets of a stream's slices; entry indices are absolute in the arena).  Which stream a read walks is a
-    // per-READ value (k_route: wsid), so one launch of k_walk serves the reads of all streams, sized without a look at
-    // the routing counters. ----
-    {
-        const size_t n_wc = f.wcrowns.size() * WC_MAX;
-        std::vector<WcInfo> info(n_wc + f.streams.size());
-        std::vector<IxHead> a_head;
-        std::vector<IxEnt> a_ent;
-        std::vector<uint8_t> a_nest, a_sp;
-        std::vector<NodeRec> a_nrec;
-        std::vector<SegNode> a_pre, a_suf, a_dst;
-        size_t tot_n = 0, tot_ent = 0, tot_head = 0, tot_sp = 0, tot_dst = 0;
-        for (const auto& wc : f.wcrowns)
-            for (const Stream& st : wc) {
-                tot_n += st.n; tot_ent += st.ix_ent.size(); tot_head += st.ix_head.size(); tot_sp += st.sp.size(); tot_dst += st.rq_dst.size();
-            }
-        const size_t wc_n = tot_n, wc_ent = tot_ent, wc_head = tot_head, wc_sp = tot_sp, wc_dst = tot_dst;   // (the window crowns' share)
-        for (const Stream& st : f.streams) {
-            tot_n += st.n; tot_ent += st.ix_ent.size(); tot_head += st.ix_head.size(); tot_sp += st.sp.size(); tot_dst += st.rq_dst.size();
-        }
-        if (tot_ent >= 0xFFFFFFF0ull || tot_n >= 0xFFFFFFF0ull || tot_head >= 0xFFFFFFF0ull || tot_dst >= 0xFFFFFFF0ull)
-            return set_error(WEPP_ELIMIT, "the walk structures exceed 2^32 index entries");
-        a_head.reserve(wc_head); a_ent.reserve(wc_ent); a_nest.reserve(wc_head); a_sp.reserve(wc_sp);
-        a_nrec.reserve(wc_n); a_pre.reserve(wc_n); a_suf.reserve(wc_n); a_dst.reserve(wc_dst);
-        for (size_t w = 0; w < f.wcrowns.size(); w++)
-            for (size_t i = 0; i < f.wcrowns[w].size(); i++) {
-                const Stream& st = f.wcrowns[w][i];
-                WcInfo& wi = info[w * WC_MAX + i];
-                const uint32_t ent_off = (uint32_t)a_ent.size();
-                wi.n = st.n;
-                wi.rq_blocks = st.rq_blocks;
-                wi.last_ent = ent_off + (uint32_t)st.ix_ent.size() - 1;
-                wi.has_pre = st.ix_pre.empty() ? 0u : st.ix_pre[0];
-                wi.node_off = (uint32_t)a_nrec.size();
-                wi.head_off = (uint32_t)a_head.size();
-                wi.nest_off = (uint32_t)a_nest.size();
-                wi.dst_off = (uint32_t)a_dst.size();
-                wi.sp_off = a_sp.size();
-                wi.tau = st.tau;
-                wi.whole = st.whole;
-                wi.whole_bfs = f.rank2bfs[st.whole.rank < f.N ? st.whole.rank : 0u];
-                for (IxHead hd : st.ix_head) { hd.off += ent_off; a_head.push_back(hd); }
-                for (IxEnt e : st.ix_ent) { if (e.up != IX_NONE) e.up += ent_off; a_ent.push_back(e); }
-                a_nest.insert(a_nest.end(), st.ix_nest.begin(), st.ix_nest.end());
-                a_nrec.insert(a_nrec.end(), st.nrec.begin(), st.nrec.end());
-                a_pre.insert(a_pre.end(), st.rq_pre.begin(), st.rq_pre.end());
-                a_suf.insert(a_suf.end(), st.rq_suf.begin(), st.rq_suf.end());
-                a_dst.insert(a_dst.end(), st.rq_dst.begin(), st.rq_dst.end());
-                a_sp.insert(a_sp.end(), st.sp.begin(), st.sp.end());
-                h->wc_nodes += st.n;
-                h->wc_count++;
-            }
-        // one device allocation per array; the window crowns' (rebased) concatenation goes to its front, every tree-wide
-        // stream's arrays are copied from the image into their slices, the entry indices of a slice rebased by a kernel
-        DevWalk arena{};                           // (n = 0: never a stream of its own)
-        auto dev_array = [&](auto*& out, size_t count, const auto& front) -> int {
-            using T = std::remove_cv_t<std::remove_reference_t<decltype(front[0])>>;
-            void* p = nullptr;
-            const size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-            hipError_t e2 = hipMalloc(&p, bytes);
-            if (e2 != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e2));
-            h->allocs.push_back(p);
-            h->stats.device_bytes += bytes;
-            if (!front.empty()) HIP_TRY(hipMemcpy(p, front.data(), front.size() * sizeof(T), hipMemcpyHostToDevice));
-            out = (T*)p;
-            return WEPP_OK;
-        };
-        IxHead* g_head; IxEnt* g_ent; uint8_t *g_nest, *g_sp; NodeRec* g_nrec; SegNode *g_pre, *g_suf, *g_dst;
-        uint32_t* g_rtpos;                         // k_route's word per head slot, derived from g_head and g_nest slice by slice (route_pos.hpp)
-#define ARR(ptr, count, front) if ((rc = dev_array(ptr, count, front)) != WEPP_OK) return rc;
-        ARR(g_head, tot_head, a_head) ARR(g_ent, tot_ent, a_ent) ARR(g_nest, tot_head, a_nest) ARR(g_sp, tot_sp, a_sp)
-        ARR(g_nrec, tot_n, a_nrec) ARR(g_pre, tot_n, a_pre) ARR(g_suf, tot_n, a_suf) ARR(g_dst, tot_dst, a_dst)
-        ARR(g_rtpos, tot_head, std::vector<uint32_t>())
-#undef ARR
-        arena.ix_head = g_head; arena.ix_ent = g_ent; arena.ix_nest = g_nest; arena.sp = g_sp;
-        arena.nrec = g_nrec; arena.rq_pre = g_pre; arena.rq_suf = g_suf; arena.rq_dst = g_dst;
-        d.rt_pos = g_rtpos;
-        for (size_t w = 0; w < f.wcrowns.size(); w++)
-            for (size_t i = 0; i < f.wcrowns[w].size(); i++) {
-                const WcInfo& wi = info[w * WC_MAX + i];
-                HIP_TRY(launch_route_pos(g_head + wi.head_off, g_nest + wi.nest_off, (uint32_t)f.wcrowns[w][i].ix_head.size(), g_rtpos + wi.head_off, nullptr));
-            }
-        {
-            size_t o_n = wc_n, o_ent = wc_ent, o_head = wc_head, o_sp = wc_sp, o_dst = wc_dst;
-            for (size_t i = 0; i < f.streams.size(); i++) {
-                const Stream& st = f.streams[i];
-                WcInfo& wi = info[n_wc + i];
-                wi.n = st.n;
-                wi.rq_blocks = st.rq_blocks;
-                wi.last_ent = (uint32_t)(o_ent + st.ix_ent.size() - 1);
-                wi.has_pre = st.ix_pre.empty() ? 0u : st.ix_pre[0];
-                wi.node_off = (uint32_t)o_n; wi.head_off = (uint32_t)o_head; wi.nest_off = (uint32_t)o_head; wi.dst_off = (uint32_t)o_dst;
-                wi.sp_off = o_sp;
-                wi.tau = st.tau;
-                wi.whole = st.whole;
-                wi.whole_bfs = f.rank2bfs[st.whole.rank < f.N ? st.whole.rank : 0u];
-#define CP(dst, off, vec) if (!vec.empty()) HIP_TRY(hipMemcpy(dst + off, vec.data(), vec.size() * sizeof(vec[0]), hipMemcpyHostToDevice));
-                CP(g_head, o_head, st.ix_head) CP(g_ent, o_ent, st.ix_ent) CP(g_nest, o_head, st.ix_nest) CP(g_sp, o_sp, st.sp)
-                CP(g_nrec, o_n, st.nrec) CP(g_pre, o_n, st.rq_pre) CP(g_suf, o_n, st.rq_suf) CP(g_dst, o_dst, st.rq_dst)
-#undef CP
-                if (o_ent) HIP_TRY(launch_rebase_index(g_head + o_head, (uint32_t)st.ix_head.size(), g_ent + o_ent, (uint32_t)st.ix_ent.size(), (uint32_t)o_ent, nullptr));
-                HIP_TRY(launch_route_pos(g_head + o_head, g_nest + o_head, (uint32_t)st.ix_head.size(), g_rtpos + o_head, nullptr));
-                // the stream's own view (plan-wise users: k_route, the chunked walks): entry indices are absolute, so the
-                // entries are addressed from the arena's base; positions and nodes are the stream's own
-                DevWalk& dw = h->walks[i];
-                dw.n = st.n; dw.rq_blocks = st.rq_blocks; dw.last_ent = wi.last_ent; dw.has_pre = wi.has_pre; dw.whole = st.whole;
-                dw.ix_head = g_head + o_head; dw.ix_ent = g_ent; dw.ix_nest = g_nest + o_head; dw.nrec = g_nrec + o_n;
-                dw.rq_pre = g_pre + o_n; dw.rq_suf = g_suf + o_n; dw.rq_dst = g_dst + o_dst; dw.sp = g_sp + o_sp;
-                o_n += st.n; o_ent += st.ix_ent.size(); o_head += st.ix_head.size(); o_sp += st.sp.size(); o_dst += st.rq_dst.size();
-            }
-            HIP_TRY(hipDeviceSynchronize());
-        }
-        d.tw_base = (uint32_t)n_wc;
-        // ... and their sweep streams, for the reads that cannot walk (k_sweep_arena): the same kind of arena; every
-        // stream keeps its own tail padding (the sweep loads past a block's events and prefetches summaries)
-        {
-            std::vector<int64_t> s_nkey;
-            std::vector<uint32_t> s_nstat, s_node0, s_eoff, s_evw, s_cpo, s_cpw;
-            std::vector<uint8_t> s_meta, s_lb;
-            std::vector<BlkSum> s_sum;
-            struct Off { size_t nkey, node0, eoff, sum, ev, cpo, cpw; };
-            std::vector<Off> offs;
-            for (const auto& wc : f.wcrowns)
-                for (const Stream& st : wc) {
-                    offs.push_back(Off{s_nkey.size(), s_node0.size(), s_eoff.size(), s_sum.size(), s_evw.size(), s_cpo.size(), s_cpw.size()});
-                    s_nkey.insert(s_nkey.end(), st.nkey.begin(), st.nkey.end());
-                    s_nstat.insert(s_nstat.end(), st.nstat.begin(), st.nstat.end());
-                    s_node0.insert(s_node0.end(), st.blk_node0.begin(), st.blk_node0.end());
-                    s_eoff.insert(s_eoff.end(), st.blk_eoff.begin(), st.blk_eoff.end());
-                    s_sum.insert(s_sum.end(), st.blk_sum.begin(), st.blk_sum.end());
-                    s_sum.resize(s_sum.size() + SUM_TAIL_PAD, st.blk_sum.empty() ? BlkSum{} : st.blk_sum.back());
-                    s_evw.insert(s_evw.end(), st.ev_word.begin(), st.ev_word.end());
-                    s_evw.resize(s_evw.size() + EV_TAIL_PAD, W_PAD);
-                    s_meta.insert(s_meta.end(), st.ev_meta.begin(), st.ev_meta.end());
-                    s_meta.resize(s_meta.size() + EV_TAIL_PAD, 0);
-                    s_lb.insert(s_lb.end(), st.ev_lb.begin(), st.ev_lb.end());
-                    s_lb.resize(s_lb.size() + EV_TAIL_PAD, 255);
-                    s_cpo.insert(s_cpo.end(), st.cp_off.begin(), st.cp_off.end());
-                    s_cpw.insert(s_cpw.end(), st.cp_word.begin(), st.cp_word.end());
-                }
-            const int64_t* d_nkey; const uint32_t *d_nstat, *d_node0, *d_eoff, *d_evw, *d_cpo, *d_cpw;
-            const uint8_t *d_meta, *d_lb; const BlkSum* d_sum;
-            UP(d_nkey, s_nkey) UP(d_nstat, s_nstat) UP(d_node0, s_node0) UP(d_eoff, s_eoff) UP(d_sum, s_sum) UP(d_evw, s_evw)
-            UP(d_meta, s_meta) UP(d_lb, s_lb) UP(d_cpo, s_cpo) UP(d_cpw, s_cpw)
-            std::vector<DevStream> ws(f.wcrowns.size() * WC_MAX, DevStream{});
-            size_t k = 0;
-            for (size_t w = 0; w < f.wcrowns.size(); w++)
-                for (size_t i = 0; i < f.wcrowns[w].size(); i++, k++) {
-                    const Stream& st = f.wcrowns[w][i];
-                    DevStream& ds = ws[w * WC_MAX + i];
-                    ds.n = st.n; ds.NB = st.NB; ds.cp_stride = st.cp_stride; ds.ncp = (uint32_t)st.cp_off.size() - 1;
-                    ds.eager = 1u; ds.tier = WC_SLOT; ds.e_pad = (uint32_t)st.E;
-                    ds.nkey = d_nkey + offs[k].nkey; ds.nstat = d_nstat + offs[k].nkey;
-                    ds.blk_node0 = d_node0 + offs[k].node0; ds.blk_eoff = d_eoff + offs[k].eoff; ds.blk_sum = d_sum + offs[k].sum;
-                    ds.ev_word = d_evw + offs[k].ev; ds.ev_meta = d_meta + offs[k].ev; ds.ev_lb = d_lb + offs[k].ev;
-                    ds.cp_off = d_cpo + offs[k].cpo; ds.cp_word = d_cpw + offs[k].cpw;
-                }
-            UP(d.wc_streams, ws)
-        }
-        UP(d.wc_info, info)
-        d.wc_windows = (uint32_t)f.wcrowns.size();
-        h->stats.n_window_crowns = h->wc_count;
-        h->stats.window_crown_nodes = h->wc_nodes;
-        h->walks.resize(MAX_STREAMS, DevWalk{});
-        h->walks[WC_SLOT] = arena;
-    }
-    UP(d.walks, h->walks)
+    WEPP_TRY(build_walk_arena(f, h));
+    WEPP_TRY(upload(h, h->walks, &d.walks));
     // k_route's routing tables: a property of the tree, built here once (device_mat.hpp: RouteTables)
     {
         const std::vector<RouteTables> blank(1);
-        UP(d.route_tab, blank)
+        WEPP_TRY(upload(h, blank, &d.route_tab));
         HIP_TRY(launch_route_tables(d, const_cast<RouteTables*>(d.route_tab), nullptr));
         HIP_TRY(hipDeviceSynchronize());
     }
@@ -377,7 +309,7 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     d.seed_sig = nullptr;
     d.seed_stride = d.seed_chunks = d.seed_row_words = 0;
     if (!f.seed_sig.empty()) {
-        UP(d.seed_sig, f.seed_sig)
+        WEPP_TRY(upload(h, f.seed_sig, &d.seed_sig));
         d.seed_stride = f.seed_stride;
         d.seed_chunks = f.seed_chunks;
         d.seed_row_words = f.seed_row_words;
@@ -389,7 +321,6 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
     h->stats.window_size = WIN_SIZE;
     h->stats.window_stride = WIN_STRIDE;
     h->stats.window_uncovered_positions = f.max_pos + 1 > MAX_WINDOWS * WIN_STRIDE ? f.max_pos + 1 - MAX_WINDOWS * WIN_STRIDE : 0;
-#undef UP
     {
         const bool walk_on = h->tun.walk;
         // k_walk keeps an open interval as (subtree end << WALK_DELTA_BITS) | delta in one dword: a stream of
@@ -399,39 +330,9 @@ int upload_flat(const FlatMAT& f, int device, wepp_mat_t** out) {
             if ((uint64_t)st.n >= (1ull << (32 - WALK_DELTA_BITS))) h->walk_ok = 0;
         h->use_walk = (walk_on && h->walk_ok) ? 1 : 0;
     }
-    // (two arrays of WALK_COUNTERS slots: loop iterations of the walks' waves, bytes their lanes asked memory for)
-    e = hipMalloc((void**)&h->d_work, wepp_mat::D_WORK_BYTES);
-    if (e == hipSuccess) e = hipMemset(h->d_work, 0, wepp_mat::D_WORK_BYTES);
-    if (e != hipSuccess) return hip_fail(e, "handle setup");
-    for (PlaceLane& L : h->lane) {
-        if (e == hipSuccess) e = hipMalloc((void**)&L.d_info, (2 * TI_WORDS + ROUTE_BLOCKS * MAX_PLANS) * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMemset(L.d_info, 0, 2 * TI_WORDS * sizeof(uint32_t));
-        // (the report block of k_step, handle.hpp: the device stores into it, the host polls its last line)
-        if (e == hipSuccess) e = hipHostMalloc((void**)&L.h_info, info_block_words(TI_WORDS) * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped);
-        if (e == hipSuccess) {
-            memset(L.h_info, 0, info_block_words(TI_WORDS) * sizeof(uint32_t));
-            e = hipHostGetDevicePointer((void**)&L.d_report, L.h_info, 0);
-        }
-        for (uint32_t i = 0; i < MAX_STREAMS && e == hipSuccess; i++) {
-            e = hipStreamCreateWithFlags(&L.side[i], hipStreamNonBlocking);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&L.join_ev[i], hipEventDisableTiming);
-        }
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&L.fork_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&L.route_ev, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&L.info_ev, hipEventDisableTiming);
-    }
-    for (uint32_t i = 0; i < wepp_mat::kRing && e == hipSuccess; i++) {
-        e = hipEventCreate(&h->ev0[i]);
-        if (e == hipSuccess) e = hipEventCreate(&h->ev1[i]);
-    }
-    if (e == hipSuccess) e = sweep_set_max_lds(160 * 1024);
-    if (e == hipSuccess) e = seed_set_max_lds(160 * 1024);
-    for (PlaceLane& L : h->lane)
-        if (e == hipSuccess && h->dev.seed_chunks) {
-            e = hipMalloc(&L.d_seed_heavy, seed_heavy_bytes());
-            if (e == hipSuccess) e = hipMemset(L.d_seed_heavy, 0, seed_heavy_bytes());
-        }
-    if (e != hipSuccess) return hip_fail(e, "handle setup");
+    HIP_TRY(sweep_set_max_lds(160 * 1024));
+    HIP_TRY(seed_set_max_lds(160 * 1024));
+    WEPP_TRY(create_call_resources(h, h->dev.seed_chunks ? seed_heavy_bytes() : 0));
     *out = owner.release();
     return WEPP_OK;
 }
@@ -460,7 +361,7 @@ extern "C" int wepp_mat_upload(const wepp_flat_t* flat, int device, wepp_mat_t**
 }
 
 extern "C" int wepp_mat_destroy(wepp_mat_t* mat) {
-    release(mat);
+    delete mat;
     return WEPP_OK;
 }
 
@@ -516,15 +417,8 @@ namespace wepp {
 // direct wepp_place_batch_device call is the whole: base 0, total n_reads) -- where its plan ids go in d_plan_of.
 // the plan id and walk-slice id of every read of a call (wepp_mat_last_plans / _crowns read them back): grow-only
 int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
-    if (plan_total <= mat->plan_of_bytes) return WEPP_OK;
-    if (mat->d_plan_of) { HIP_TRY(hipDeviceSynchronize()); (void)hipFree(mat->d_plan_of); mat->d_plan_of = nullptr; mat->plan_of_bytes = 0; }
-    if (mat->d_wsid_of) { (void)hipFree(mat->d_wsid_of); mat->d_wsid_of = nullptr; }
-    const size_t need = (size_t)plan_total + plan_total / 4 + 256;
-    hipError_t e = hipMalloc((void**)&mat->d_plan_of, need);
-    if (e == hipSuccess) e = hipMalloc((void**)&mat->d_wsid_of, need * 4);
-    if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc plan ids: ") + hipGetErrorString(e));
-    mat->plan_of_bytes = need;
-    return WEPP_OK;
+    WEPP_TRY(mat->d_plan_of.reserve(plan_total, 4, "plan ids"));
+    return mat->d_wsid_of.reserve((size_t)plan_total * 4, 4, "plan ids");
 }
 
 // Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes, and
@@ -603,10 +497,10 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     {
         // (half as much again, as ever; a device-wide synchronisation in front of the free: the lane's previous call may
         // still run out of these regions)
-        const int rc = grow_only(L.ws, L.ws_bytes, carve(nullptr), 2, false, "workspace");
+        const int rc = L.ws.reserve(carve(nullptr), 2, "workspace");
         if (rc != WEPP_OK) return rc;
     }
-    carve(L.ws);
+    carve(L.ws.ptr);
     uint32_t* const tier_info = L.d_info + L.info_idx * TI_WORDS;
     uint32_t* const blk_counts = L.d_info + 2 * TI_WORDS;
 
@@ -1009,11 +903,11 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     {
         // (half as much again: the partials of a batch of long reads vary by a third with the tile size its longest
         // read allows, and a regrowth costs a hipFree + hipMalloc of ~100 MB, 16 ms)
-        const int rc = grow_only(L.part, L.part_bytes, part_need, 2, false, "partials");
+        const int rc = L.part.reserve(part_need, 2, "partials");
         if (rc != WEPP_OK) return rc;
     }
     if (!scattered && (np || arena_n || seed_n || walkc[0].n || walkc[1].n)) return set_error(WEPP_EDEVICE, "a planned launch without its read list");
-    char* const part_base = (char*)L.part;
+    char* const part_base = (char*)L.part.ptr;
     const bool debug_plans = tun.debug_plans;
     for (uint32_t i = 0; i < np; i++) {
         Plan& p = plans[i];
@@ -1277,6 +1171,24 @@ extern "C" int wepp_place_batch_device(wepp_mat_t* mat, const uint32_t* d_read_o
                         (hipStream_t)hip_stream, 0, n_reads);
 }
 
+namespace {
+// `n` slots of the handle's device counters from slot `first` on (handle.hpp: d_work)
+int read_work_slots(wepp_mat_t* mat, uint32_t first, uint32_t n, unsigned long long* out) {
+    HIP_TRY(hipMemcpy(out, mat->d_work + first, n * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    return WEPP_OK;
+}
+
+// the plan id of every read of the handle's most recent placement call, for the diagnostics that decode it
+int read_last_plans(wepp_mat_t* mat, uint8_t* plan_ids, uint32_t n_reads) {
+    if (n_reads != mat->last_n_reads || !mat->d_plan_of)
+        return set_error(WEPP_EINVAL, "n_reads differs from the handle's last placement call");
+    HIP_TRY(hipSetDevice(mat->device));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(plan_ids, mat->d_plan_of, n_reads, hipMemcpyDeviceToHost));
+    return WEPP_OK;
+}
+}  // namespace
+
 extern "C" int wepp_mat_timing_reset(wepp_mat_t* mat) {
     if (!mat) return set_error(WEPP_EINVAL, "null argument");
     mat->n_timed = 0;
@@ -1305,11 +1217,9 @@ extern "C" int wepp_mat_last_timing(wepp_mat_t* mat, float* mean_sweep_ms, uint3
     // sparse-table bytes and range-query aggregates actually requested, list heads, read words, start states of
     // the jobs, results); averaged over the calls since the reset
     unsigned long long wb = 0;
-    {
-        std::vector<unsigned long long> slots(WALK_COUNTERS);
-        HIP_TRY(hipMemcpy(slots.data(), mat->d_work + WALK_COUNTERS, WALK_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (unsigned long long v : slots) wb += v;
-    }
+    std::vector<unsigned long long> slots(WALK_COUNTERS);
+    WEPP_TRY(read_work_slots(mat, WALK_COUNTERS, WALK_COUNTERS, slots.data()));
+    for (unsigned long long v : slots) wb += v;
     if (mean_sweep_ms) *mean_sweep_ms = (float)(sum / n);
     if (n_calls) *n_calls = n;
     if (passes) *passes = mat->acc_passes / std::max<uint64_t>(1, mat->n_timed);
@@ -1320,11 +1230,7 @@ extern "C" int wepp_mat_last_timing(wepp_mat_t* mat, float* mean_sweep_ms, uint3
 // diagnostic: the sweep stream every read of the handle's most recent placement call was routed to
 extern "C" int wepp_mat_last_tiers(wepp_mat_t* mat, uint8_t* tiers, uint32_t n_reads) {
     if (!mat || !tiers) return set_error(WEPP_EINVAL, "null argument");
-    if (n_reads != mat->last_n_reads || !mat->d_plan_of)
-        return set_error(WEPP_EINVAL, "n_reads differs from the handle's last placement call");
-    HIP_TRY(hipSetDevice(mat->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(tiers, mat->d_plan_of, n_reads, hipMemcpyDeviceToHost));
+    WEPP_TRY(read_last_plans(mat, tiers, n_reads));
     for (uint32_t r = 0; r < n_reads; r++)       // the workspace holds plan ids (device_mat.hpp: plan_id)
         tiers[r] = (plan_class(tiers[r]) == PLAN_WIN || plan_class(tiers[r]) == PLAN_SEED) ? (uint8_t)(mat->dev.n_streams - 1) : (uint8_t)plan_index(tiers[r]);
     return WEPP_OK;
@@ -1333,11 +1239,7 @@ extern "C" int wepp_mat_last_tiers(wepp_mat_t* mat, uint8_t* tiers, uint32_t n_r
 // diagnostic: the full plan id (class and stream) of every read of the handle's most recent placement call
 extern "C" int wepp_mat_last_plans(wepp_mat_t* mat, uint8_t* plan_class_out, uint8_t* plan_stream_out, uint32_t n_reads) {
     if (!mat || !plan_class_out || !plan_stream_out) return set_error(WEPP_EINVAL, "null argument");
-    if (n_reads != mat->last_n_reads || !mat->d_plan_of)
-        return set_error(WEPP_EINVAL, "n_reads differs from the handle's last placement call");
-    HIP_TRY(hipSetDevice(mat->device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(plan_stream_out, mat->d_plan_of, n_reads, hipMemcpyDeviceToHost));
+    WEPP_TRY(read_last_plans(mat, plan_stream_out, n_reads));
     for (uint32_t r = 0; r < n_reads; r++) {
         const uint32_t id = plan_stream_out[r];
         plan_class_out[r] = (uint8_t)plan_class(id);
@@ -1349,14 +1251,10 @@ extern "C" int wepp_mat_last_plans(wepp_mat_t* mat, uint8_t* plan_class_out, uin
 // diagnostic: the window crown (window, crown of the window) of every read of the last call that walked one
 extern "C" int wepp_mat_last_crowns(wepp_mat_t* mat, uint8_t* window_out, uint8_t* crown_out, uint32_t n_reads) {
     if (!mat || !window_out || !crown_out) return set_error(WEPP_EINVAL, "null argument");
-    if (n_reads != mat->last_n_reads || !mat->d_plan_of)
-        return set_error(WEPP_EINVAL, "n_reads differs from the handle's last placement call");
-    HIP_TRY(hipSetDevice(mat->device));
-    HIP_TRY(hipDeviceSynchronize());
     std::vector<uint32_t> sid(n_reads);
     std::vector<uint8_t> plan(n_reads);
+    WEPP_TRY(read_last_plans(mat, plan.data(), n_reads));
     HIP_TRY(hipMemcpy(sid.data(), mat->d_wsid_of, (size_t)n_reads * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(plan.data(), mat->d_plan_of, n_reads, hipMemcpyDeviceToHost));
     for (uint32_t r = 0; r < n_reads; r++) {
         const bool in_arena = plan_class(plan[r]) != PLAN_WIN && plan_class(plan[r]) != PLAN_SWEEP && plan_index(plan[r]) == WC_SLOT;
         window_out[r] = in_arena ? (uint8_t)(sid[r] / WC_MAX) : (uint8_t)255;
@@ -1371,16 +1269,12 @@ extern "C" int wepp_mat_last_walk(wepp_mat_t* mat, uint64_t* reads_walked, uint6
     HIP_TRY(hipSetDevice(mat->device));
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long it = 0;
-    {
-        std::vector<unsigned long long> slots(WALK_COUNTERS);
-        HIP_TRY(hipMemcpy(slots.data(), mat->d_work, WALK_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-        for (unsigned long long v : slots) it += v;
-    }
+    std::vector<unsigned long long> slots(WALK_COUNTERS);
+    WEPP_TRY(read_work_slots(mat, 0, WALK_COUNTERS, slots.data()));
+    for (unsigned long long v : slots) it += v;
     if (reads_walked) *reads_walked = mat->last_walk_reads;
     if (walk_iterations) *walk_iterations = it;
     if (mat->tun.walk_debug) {
-        std::vector<unsigned long long> slots(WALK_COUNTERS);
-        HIP_TRY(hipMemcpy(slots.data(), mat->d_work, WALK_COUNTERS * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long a = 0, b = 0;
         for (uint32_t i = 0; i < WALK_COUNTERS / 2; i++) { a += slots[i]; b += slots[WALK_COUNTERS / 2 + i]; }
         fprintf(stderr, "[walk] wave-iterations since reset: plain %llu chunked %llu\n", a, b);
@@ -1408,7 +1302,7 @@ extern "C" int wepp_mat_last_seeds(wepp_mat_t* mat, uint64_t* samples, uint64_t*
     HIP_TRY(hipSetDevice(mat->device));
     HIP_TRY(hipDeviceSynchronize());
     unsigned long long v[12] = {};
-    HIP_TRY(hipMemcpy(v, mat->d_work + 2 * WALK_COUNTERS, sizeof(v), hipMemcpyDeviceToHost));
+    WEPP_TRY(read_work_slots(mat, 2 * WALK_COUNTERS, 12, v));
     if (samples) *samples = v[0];
     if (chunks_evaluated) *chunks_evaluated = v[1];
     if (chunks_total) *chunks_total = v[2];

@@ -60,16 +60,7 @@ struct DevPool {                       // device allocations of one call, taken 
 #define DEV_GET(pool, p, n) /* p = n elements from the pool, or the caller returns WEPP_ENOMEM */ \
     do { if (hipError_t _e = (pool).get(&(p), (n))) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(_e)); } while (0)
 
-template <int N> struct DevEvents {                     // the N events of a call; destroys those that were created
-    hipEvent_t ev[N] = {};
-    int n = 0;                         // created so far
-    ~DevEvents() { while (n > 0) (void)hipEventDestroy(ev[--n]); }
-    int create() {
-        for (; n < N; n++) { hipEvent_t& x = ev[n]; HIP_TRY(hipEventCreate(&x)); }
-        return WEPP_OK;
-    }
-    hipEvent_t operator[](int i) const { return ev[i]; }
-};
+// (the events of a call: DevEvents of handle.hpp)
 
 // the reference's preconditions on a read batch, made explicit (read_off / start / end / degree are non-null when n_reads > 0,
 // read_word when there are words): WEPP_OK, or WEPP_EINVAL with the message set.  *total_degree receives the sum of the degrees.

@@ -43,7 +43,15 @@ int prepare_handle(wepp_mat_t* mat) {
     // reverse pre-order visits children before parents
     for (uint32_t d = 0; d < N; d++) end[d] = d + 1;
     for (uint32_t d = N; d-- > 1;) end[parent[d]] = std::max(end[parent[d]], end[d]);
-    return upload(mat, end, &mat->nbr_dfs_end);
+    // (the handle takes the block once it is filled: a call that fails here leaves none, and the next one tries again)
+    DevMem<uint32_t> d_end;
+    const size_t bytes = std::max<size_t>((size_t)N * 4, 16);
+    const hipError_t e = hipMalloc((void**)&d_end.ptr, bytes);
+    if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
+    HIP_TRY(hipMemcpy(d_end, end.data(), (size_t)N * 4, hipMemcpyHostToDevice));
+    std::swap(mat->nbr_dfs_end.ptr, d_end.ptr);
+    mat->stats.device_bytes += bytes;
+    return WEPP_OK;
 }
 
 // Both entry points.  out != nullptr: the regions; dist != nullptr: the field.

@@ -18,8 +18,8 @@ namespace {
 // Grow-only buffers of the handle for the pass-2 calls: `dev_bytes` of device memory in io_in and `pin_bytes`
 // of pinned staging (the same buffers wepp_place_batch uses; the calls on a handle are serial).
 int reserve_io(wepp_mat* mat, size_t dev_bytes, size_t pin_need) {
-    const int rc = grow_only(mat->io_in, mat->io_in_bytes, dev_bytes, 4, false, "io buffer");
-    return rc != WEPP_OK ? rc : grow_only(mat->pin, mat->pin_bytes, pin_need, 4, true, "staging buffer");
+    WEPP_TRY(mat->io_in.reserve(dev_bytes, 4, "io buffer"));
+    return mat->pin.reserve(pin_need, 4, "staging buffer");
 }
 
 // The regions of a block, one behind the other, each padded to 256 bytes: take<T>(bytes) is the next one.  The same
@@ -77,7 +77,7 @@ extern "C" int wepp_imputed_mutations(wepp_mat_t* mat, const uint32_t* read_off,
     };
     const Block size = lay_out(nullptr, false);
     WEPP_TRY(reserve_io(mat, size.bytes, size.up));
-    const Block h = lay_out((char*)mat->pin, true), d = lay_out((char*)mat->io_in, false);
+    const Block h = lay_out((char*)mat->pin.ptr, true), d = lay_out((char*)mat->io_in.ptr, false);
     std::memcpy(h.off, read_off, (size_t)(n_reads + 1) * 4);
     if (nw) std::memcpy(h.word, read_word, nw * 4);
     std::memcpy(h.best, best_bfs_j, (size_t)n_reads * 4);
@@ -130,13 +130,13 @@ extern "C" int wepp_excess_mutations(wepp_mat_t* mat, const uint32_t* read_off, 
     char* hp = nullptr;
     Block d{};
     auto stage_inputs = [&]() -> int {
-        hp = (char*)mat->pin;
+        hp = (char*)mat->pin.ptr;
         const Block h = lay_out(hp, true);
         std::memcpy(h.off, read_off, (size_t)(n_reads + 1) * 4);
         if (nw) std::memcpy(h.word, read_word, nw * 4);
         std::memcpy(h.pr, pair_read, (size_t)n_pairs * 4);
         std::memcpy(h.pj, pair_bfs_j, (size_t)n_pairs * 4);
-        d = lay_out((char*)mat->io_in, false);
+        d = lay_out((char*)mat->io_in.ptr, false);
         HIP_TRY(hipMemcpy(d.off, h.off, size.up, hipMemcpyHostToDevice));
         return WEPP_OK;
     };
@@ -154,9 +154,9 @@ extern "C" int wepp_excess_mutations(wepp_mat_t* mat, const uint32_t* read_off, 
     if (!exc_pos || !exc_ref || !exc_par || !exc_mut) return set_error(WEPP_EINVAL, "null output array");
     {
         // the device buffer may move when it grows: the inputs are uploaded again behind the new base
-        const bool grows = size.fixed + pad256(total * 4) > mat->io_in_bytes;
+        const bool grows = size.fixed + pad256(total * 4) > mat->io_in.bytes;
         WEPP_TRY(reserve_io(mat, size.fixed + pad256(total * 4), std::max({size.up, b_ooff, (size_t)total * 4})));
-        hp = (char*)mat->pin;
+        hp = (char*)mat->pin.ptr;
         if (grows) WEPP_TRY(stage_inputs());
     }
     {
@@ -218,8 +218,8 @@ extern "C" int wepp_best_nodes(wepp_mat_t* mat, const uint32_t* read_off, const 
     };
     const Block size = lay_out(nullptr, false);
     WEPP_TRY(reserve_io(mat, size.bytes, std::max(size.up, (size_t)total * 4)));
-    char* hp = (char*)mat->pin;
-    const Block h = lay_out(hp, true), d = lay_out((char*)mat->io_in, false);
+    char* hp = (char*)mat->pin.ptr;
+    const Block h = lay_out(hp, true), d = lay_out((char*)mat->io_in.ptr, false);
     std::memcpy(h.off, read_off, (size_t)(n_reads + 1) * 4);
     if (nw) std::memcpy(h.word, read_word, nw * 4);
     std::memcpy(h.best, score, (size_t)n_reads * 4);

@@ -13,7 +13,7 @@
 #include <thread>
 #include <vector>
 
-#include "handle.hpp"
+#include "handle_setup.hpp"
 #include "host_pool.hpp"
 #include "read_check.hpp"
 
@@ -51,22 +51,7 @@ extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const
     const auto t_begin = std::chrono::steady_clock::now();
     auto since = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count(); };
 
-    hipError_t e = hipSuccess;
-    if (!mat->pipe_h2d[0]) {
-        for (hipStream_t& st : mat->pipe_h2d)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (hipStream_t& st : mat->pipe_compute)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (hipStream_t& st : mat->pipe_d2h)
-            if (e == hipSuccess) e = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-        for (uint32_t i = 0; i < wepp_mat::kPipeMax && e == hipSuccess; i++) {
-            e = hipEventCreateWithFlags(&mat->pipe_up[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&mat->pipe_done[i], hipEventDisableTiming);
-        }
-        for (uint32_t i = 0; i < 4 * wepp_mat::kPipeMax && e == hipSuccess; i++)
-            e = hipEventCreateWithFlags(&mat->pipe_out[i], hipEventDisableTiming);
-        if (e != hipSuccess) return hip_fail(e, "pipeline streams / events");
-    }
+    WEPP_TRY(create_pipeline(mat));
     // ---- buffers: grow-only, on the handle (no hipMalloc / hipFree per call) ----
     const size_t off_bytes = (((size_t)(n_reads + 1) * 4) + 255) & ~(size_t)255;
     const size_t in_need = off_bytes + std::max<size_t>(nw * 4, 16), out_need = (size_t)n_reads * 16;
@@ -75,19 +60,16 @@ extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const
     bool out_pinned[4];
     bool any_staged_out = false;
     for (int i = 0; i < 4; i++) { out_pinned[i] = dst[i] && is_pinned_host(dst[i]); any_staged_out = any_staged_out || (dst[i] && !out_pinned[i]); }
-    {
-        int rc = grow_only(mat->io_in, mat->io_in_bytes, in_need, 4, false, "reads of the batch");
-        if (rc == WEPP_OK) rc = grow_only(mat->io_out, mat->io_out_bytes, out_need, 4, false, "results of the batch");
-        if (rc == WEPP_OK && !in_pinned) rc = grow_only(mat->pin, mat->pin_bytes, in_need, 4, true, "reads of the batch");
-        if (rc == WEPP_OK && any_staged_out) rc = grow_only(mat->pin_out, mat->pin_out_bytes, out_need, 4, true, "results of the batch");
-        if (rc != WEPP_OK) return rc;
-    }
-    uint32_t* const d_off = (uint32_t*)mat->io_in;
-    uint32_t* const d_word = (uint32_t*)((char*)mat->io_in + off_bytes);
-    uint32_t* const d_out = (uint32_t*)mat->io_out;
-    uint32_t* const pin_off = in_pinned ? nullptr : (uint32_t*)mat->pin;
-    uint32_t* const pin_word = in_pinned ? nullptr : (uint32_t*)((char*)mat->pin + off_bytes);
-    uint32_t* const po = (uint32_t*)mat->pin_out;
+    WEPP_TRY(mat->io_in.reserve(in_need, 4, "reads of the batch"));
+    WEPP_TRY(mat->io_out.reserve(out_need, 4, "results of the batch"));
+    if (!in_pinned) WEPP_TRY(mat->pin.reserve(in_need, 4, "reads of the batch"));
+    if (any_staged_out) WEPP_TRY(mat->pin_out.reserve(out_need, 4, "results of the batch"));
+    uint32_t* const d_off = (uint32_t*)mat->io_in.ptr;
+    uint32_t* const d_word = (uint32_t*)((char*)mat->io_in.ptr + off_bytes);
+    uint32_t* const d_out = (uint32_t*)mat->io_out.ptr;
+    uint32_t* const pin_off = in_pinned ? nullptr : (uint32_t*)mat->pin.ptr;
+    uint32_t* const pin_word = in_pinned ? nullptr : (uint32_t*)((char*)mat->pin.ptr + off_bytes);
+    uint32_t* const po = (uint32_t*)mat->pin_out.ptr;
 
     // ---- sub-batches and tasks (read_check.hpp: batch_geometry) ----
     if (n_reads >= BIG_BATCH_READS && !mat->pool) {
@@ -277,7 +259,7 @@ extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const
     if (per_node_scores) {
         int32_t* d_pns = nullptr;
         const size_t nb = (size_t)n_reads * mat->dev.N * sizeof(int32_t);
-        e = hipMalloc((void**)&d_pns, nb);
+        hipError_t e = hipMalloc((void**)&d_pns, nb);
         if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc per_node_scores: ") + hipGetErrorString(e));
         if (mat->tun.debug_plans) {
             const DevStream& full = mat->streams.back();
