@@ -3,7 +3,7 @@ launch rule of wepp_place_batch restated in plain Python.
 
 Two halves:
   * plan arithmetic -- tile_reads, takes_table, ent_cap, key_cap, chunks, finalize_lanes_per_read: the rule of
-    capi.cpp ("plan the launches") and device_mat.hpp written again as pure functions.  The GPU tests compare the
+    launch_plan.hpp (plan_launches) and device_mat.hpp written again as pure functions.  The GPU tests compare the
     library's `[plan]` lines (WEPP_DEBUG_PLANS=1) with predict_plan().
   * builders -- CASES[name]() returns a Case: tree, reads, the knobs that send the reads to the sweep in question and
     `facts`, statements about the INPUT (entry counts, hit events per block of the flat image, positions against the

@@ -2,7 +2,7 @@
 
 A lane owns two grow-only device blocks.  `ws` holds the regions sized by the number of reads alone; it is grown before
 k_route and never moves during a call.  `part` holds the partials of the sweep plans, 12 bytes per (chunk, read), sized
-only when the routing counters are back; it is grown behind the plan loop, before anything of the call touches it.  So
+only when the routing counters are back; it is grown behind the planner, before anything of the call touches it.  So
 a call whose partials do not fit routes once, like every other call: WEPP_DEBUG_PLANS=1 prints one "[route]" and one
 "[step]" line per call.  (While both shared one block, such a call freed the block under its own routing, allocated a
 larger one and routed a second time: two "[step]" lines.)

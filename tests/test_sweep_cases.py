@@ -3,7 +3,11 @@ the fact about its INPUT that makes it an edge case -- entry counts on both side
 of the flat image, positions against the tile's smallest one, chunk lengths, oracle answers that change with the word
 a confused kernel would misread.  A generator that drifts cannot hollow a case out unnoticed.  Every case on a small
 tree also goes through the Python model of the sweep (tests/sweep_model.py), cut into the chunks the rule predicts,
-against the oracle."""
+against the oracle.  The library's own planner (wepp_amd/csrc/launch_plan.hpp) is held to the same rule without a GPU:
+tests/cxx/launch_plan_main.cpp plans every tile case and prints the `[plan]` lines the device call would."""
+import os
+import subprocess
+
 import numpy as np
 import pytest
 
@@ -285,3 +289,123 @@ def test_model_of_the_sweep_on_the_cases(oracle, name):
     for r, exp in zip(pick, want):
         got = fm.place_full(lists[r], nchunks=nchunks)
         assert (got["score"], got["best_j"], got["num_best"], got["has_unique"]) == exp, (name, r)
+
+
+# ---- the library's planner on the cases, without a GPU ----------------------------------------------------------------
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAX_STREAMS, MAX_WINDOWS = 16, 32          # flatmat.hpp
+PLAN_SWEEP, PLAN_WIN_BASE, WC_SLOT = 2, 5 * MAX_STREAMS, MAX_STREAMS - 1      # device_mat.hpp: plan id = class * MAX_STREAMS + stream
+PLAN_SEED_ID = PLAN_WIN_BASE + MAX_WINDOWS
+WEPP_EDEVICE, WEPP_ELIMIT = 3, 4           # include/wepp_place.h
+
+
+@pytest.fixture(scope="module", params=["plain", "sanitized"])
+def planner(request, tmp_path_factory):
+    """tests/cxx/launch_plan_main.cpp built against the emulated runtime's headers, plain and under ASan + UBSan."""
+    tmp = tmp_path_factory.mktemp("launch_plan_" + request.param)
+    flags = ["-O1"]
+    if request.param == "sanitized":
+        probe = tmp / "probe.cpp"
+        probe.write_text("int main() { return 0; }\n")
+        can = subprocess.run(["g++", "-fsanitize=address,undefined", str(probe), "-o", str(tmp / "probe")], capture_output=True, text=True)
+        if can.returncode != 0:
+            pytest.skip("no sanitizer runtime: " + can.stderr[-200:])
+        flags = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
+    exe = str(tmp / "launch_plan_main")
+    srcs = [os.path.join(ROOT, "tests", "cxx", "launch_plan_main.cpp"), os.path.join(ROOT, "wepp_amd", "csrc", "errors.cpp")]
+    build = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Wno-unused-parameter", *flags, "-I", os.path.join(ROOT, "tests", "cxx", "hip_emu"),
+                            *srcs, "-o", exe], capture_output=True, text=True)
+    assert build.returncode == 0, build.stderr[-3000:]
+
+    def run(T, tree, streams, wstreams, triples, walking=0, fuse_windows=1):
+        """tree = (bm_words, max_pos, seed_chunks, wc_windows); streams / wstreams: geometries; triples: (plan id, count, maxk)."""
+        geo = lambda g: "%d %d %d %d" % (g["NB"], g["ncp"], g["cp_stride"], g["sbytes"])
+        text = "\n".join(["%d %d %d" % (T, walking, fuse_windows), "%d %d %d %d %d" % (tree[0], tree[1], len(streams), tree[2], tree[3])] + [geo(g) for g in streams]
+                         + [str(len(wstreams))] + [geo(g) for g in wstreams] + [str(len(triples))] + ["%d %d %d" % t for t in triples]) + "\n"
+        return subprocess.run([exe], input=text, capture_output=True, text=True, timeout=60, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    return run
+
+
+def _problem(c, count):
+    """The planning problem of the call that places the first `count` reads of a tile case: its one plan id with the
+    case's geometry on the stream that id names (the other streams are never asked about)."""
+    maxk = int(max(1, _k(c)[:count].max()))
+    tree = (c.info.bm_words, c.info.max_pos, 0, 0)
+    ns = int(c.info.flat.n_streams)
+    none = dict(NB=1, ncp=1, cp_stride=1, sbytes=0)
+    if c.window is None:
+        return tree, [none] * (ns - 1) + [sc.stream_geometry(c.info.flat)], [], [(PLAN_SWEEP * MAX_STREAMS + ns - 1, count, maxk)]
+    return tree, [none] * ns, [none] * c.window + [sc.stream_geometry(c.info.flat, "w%d" % c.window)], [(PLAN_WIN_BASE + c.window, count, maxk)]
+
+
+TILE_CASES = sorted(n for n in sc.CASES if not n.startswith("arena_"))
+
+
+def test_every_case_without_a_plan_line_is_an_arena_case():
+    assert all((sc.CASES[n]().arena is None) == (n in TILE_CASES) for n in sc.CASES) and len(TILE_CASES) == len(sc.CASES) - len(sc.ARENA_CROWNS)
+
+
+def _plan_output(text):
+    """(`[plan]` lines parsed, the `[launch]` line as a dict: the partition as index lists, the totals as numbers)."""
+    rows = text.splitlines()
+    assert rows and rows[-1].startswith("[launch] ") and all(r.startswith("[plan] ") for r in rows[:-1]), text
+    launch = {}
+    for kv in rows[-1].split()[1:]:
+        k, v = kv.split("=")
+        launch[k] = [int(x) for x in v.split(",") if x] if k in ("plain", "windows", "others") else v if "@" in v else int(v)
+    return [sc.parse_plan_line(r) for r in rows[:-1]], launch
+
+
+def test_planner_on_several_plans(planner):
+    """A call with a dense plan on stream 2, a plain one on the whole tree, window-crown sweeps and a table window plan:
+    the plans in plan-id order, each behind the partials of those before it, the arena's between; the partition with the
+    window plans fused and not; passes = tiles + arena reads, bytes = tiles x stream bytes (no walks in the call)."""
+    small, whole, win = dict(NB=40, ncp=40, cp_stride=1, sbytes=20000), dict(NB=300, ncp=150, cp_stride=2, sbytes=3 << 20), dict(NB=26, ncp=26, cp_stride=1, sbytes=9000)
+    max_pos, ns = 2000, 7
+    triples = [(PLAN_SWEEP * MAX_STREAMS + 2, 10, 18), (PLAN_SWEEP * MAX_STREAMS + ns - 1, 70, 5), (PLAN_SWEEP * MAX_STREAMS + WC_SLOT, 6, 20), (PLAN_WIN_BASE + 1, 70, 40)]
+    for fuse in (1, 0):
+        run = planner(64, (64, max_pos, 0, 1), [small] * (ns - 1) + [whole], [win, win], triples, fuse_windows=fuse)
+        assert run.returncode == 0, (run.stdout, run.stderr[-2000:])
+        lines, launch = _plan_output(run.stdout)
+        want = [sc.predict_plan(10, 18, small, max_pos), sc.predict_plan(70, 5, whole, max_pos),
+                sc.predict_plan(70, 40, win, max_pos, window=1, win_tiles=2 if fuse else None)]
+        assert [{k: l[k] for k in sc.PLAN_FIELDS} for l in lines] == want, (fuse, lines, want)
+        assert [l["t"] for l in lines] == [2, ns - 1, ns - 1] and [l["off"] for l in lines] == [0, 10, 86]
+        size = [12 * w["nchunks"] * w["count"] for w in want]
+        arena_part = size[0] + size[1]
+        assert [l["part_off"] for l in lines] == [0, size[0], arena_part + 12 * sc.ARENA_CHUNKS * 6], (fuse, lines)
+        assert launch["arena"] == "6@%d" % arena_part and launch["part_total"] == sum(size) + 12 * sc.ARENA_CHUNKS * 6 and launch["seeds"] == 0
+        assert (launch["plain"], launch["windows"], launch["others"]) == (([1], [2], [0]) if fuse else ([1], [], [0, 2])), (fuse, launch)
+        assert launch["passes"] == sum(w["ntiles"] for w in want) + 6 and launch["walk_reads"] == 0
+        assert launch["bytes"] == sum(w["ntiles"] * g["sbytes"] for w, g in zip(want, (small, whole, win)))
+
+
+@pytest.mark.parametrize("name", TILE_CASES)
+def test_planner_on_the_cases(planner, name):
+    c = sc.CASES[name]()
+    for count in c.counts:
+        tree, streams, wstreams, triples = _problem(c, count)
+        run = planner(c.knobs["tile"], tree, streams, wstreams, triples)
+        assert run.returncode == 0, (name, count, run.stdout[-500:], run.stderr[-2000:])
+        lines, launch = _plan_output(run.stdout)
+        assert len(lines) == 1, (name, count, run.stdout)
+        assert {k: lines[0][k] for k in sc.PLAN_FIELDS} == c.plan(count), (name, count, lines[0], c.plan(count))
+        # the one plan: at the front of the partials, in the part of the partition its kind belongs to
+        kind = "windows" if c.window is not None and lines[0]["dense"] else "others" if lines[0]["dense"] or not lines[0]["ent_cap"] else "plain"
+        assert lines[0]["part_off"] == 0 and launch["part_total"] == 12 * lines[0]["nchunks"] * count, (name, count, run.stdout)
+        assert {k: launch[k] for k in ("plain", "windows", "others")} == {k: [0] if k == kind else [] for k in ("plain", "windows", "others")}, (name, launch)
+        assert launch["passes"] == lines[0]["ntiles"], (name, launch)
+
+
+def test_planner_errors(planner):
+    g = dict(NB=64, ncp=64, cp_stride=1, sbytes=30000)
+    for what, tree, triples, code, message in (
+            ("a plan id beyond the window plans' and the seeds'", (64, 2000, 0, 0), [(PLAN_SEED_ID + 1, 5, 5)], WEPP_EDEVICE, "routing produced an invalid plan id"),
+            ("PLAN_SEED on a handle without signatures", (64, 2000, 0, 0), [(PLAN_SEED_ID, 5, 70)], WEPP_EDEVICE, "routing produced an invalid plan id"),
+            ("count * ARENA_CHUNKS at 2^31", (64, 2000, 0, 1), [(PLAN_SWEEP * MAX_STREAMS + WC_SLOT, (1 << 31) // sc.ARENA_CHUNKS, 20)], WEPP_ELIMIT,
+             "too many window-crown sweeps in one call; split the batch")):
+        run = planner(64, tree, [g] * 7, [g], triples)
+        assert run.returncode == 3 and run.stdout == "error %d: %s\n" % (code, message), (what, run.stdout, run.stderr[-2000:])
+    # (one below the limit plans)
+    run = planner(64, (64, 2000, 0, 1), [g] * 7, [g], [(PLAN_SWEEP * MAX_STREAMS + WC_SLOT, (1 << 31) // sc.ARENA_CHUNKS - 1, 20)])
+    assert run.returncode == 0 and _plan_output(run.stdout)[0] == [], (run.stdout, run.stderr[-2000:])

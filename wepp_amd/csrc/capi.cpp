@@ -18,6 +18,7 @@
 
 #include "handle_setup.hpp"
 #include "info_wait.hpp"
+#include "launch_plan.hpp"
 
 namespace wepp {
 
@@ -421,282 +422,317 @@ int ensure_plan_buffers(wepp_mat_t* mat, uint32_t plan_total) {
     return mat->d_wsid_of.reserve((size_t)plan_total * 4, 4, "plan ids");
 }
 
-// Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes, and
-// even with one host thread their kernels may overlap on the device (each lane has its own compute stream).  Each lane
-// has its own two device blocks (handle.hpp: the fixed regions, grown before k_route, and the partials, grown once the
-// routing counters are back: a call routes once, whatever its partials need), routing counters, side streams, events
-// and k_seed second-pass table.  What they share on the handle:
-//   - the tree and everything built from it (read-only here);
-//   - the event ring (a slot claimed atomically);
-//   - the hints job_events, ww_by_jobs, step_walkers, expect_jobs8 and expect_lists (atomics; they choose how the next call cuts its work, never its results);
-//   - the call statistics (stat_mu) and the device counters d_work (device atomics, summed over both lanes);
-//   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
-int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
-                 uint32_t* d_best_bfs_j, int32_t* d_score, uint32_t* d_num_best, uint32_t* d_flags, hipStream_t stream,
-                 uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx) {
-    PlaceLane& L = mat->lane[lane_idx];
-    {
-        // (a pipelined wepp_place_batch has sized them for the whole call before its sub-batches start, on one thread)
-        const int prc = ensure_plan_buffers(mat, plan_total);
-        if (prc != WEPP_OK) return prc;
-    }
-    const uint32_t T = mat->tile_reads;
-    const uint32_t ns = mat->dev.n_streams;
+// ---- one placement call: place_device() below is a sequence of stages over one PlaceCall ----
+namespace {
 
-    // ---- the lane's two device blocks (handle.hpp: PlaceLane) ----
-    // L.ws, the fixed regions: sized by n_reads alone and grown here, before k_route writes into them, so they stay
-    // where they are for the whole call.  L.part, the partials: sized from the routing counters and grown behind the plan
-    // loop below, before anything of this call has touched it.
+// The fixed regions of the lane's first block (handle.hpp: PlaceLane::ws), in the order they lie there.
+constexpr uint32_t N_SORTS = 5;      // sort temp of the whole-tree plan and of the four walk classes (their sorts run on different side streams)
+struct LaneRegions {
+    uint32_t *list, *slot_in_blk, *key_in, *key_out, *val_in;      // val_in: the sorted lists (same offsets as in `list`)
+    uint32_t* job_n;                 // jobs of every read whose walk is cut into chunks (k_route)
+    uint32_t *wlist[2], *wwlist;     // the plain walk classes' reads that have events in their stream (k_route appends them); reads with many events, a wave each (wave_kernels.hip)
+    uint32_t *b_first, *b_clist[2], *b_jobs[2], *b_pr[2], *b_pc[2];   // the chunked classes sized blind (k_route's tables)
+    int32_t *b_ps[2], *root_score;
+    void* sort_tmp;
+    size_t sort_temp, bytes;         // bytes of one of the N_SORTS sort regions; of the block
+};
+
+// One cursor over the regions: run from a null base it gives the block's size (bytes), run from L.ws the pointers.
+LaneRegions carve_lane(void* base, uint32_t n_reads, size_t sort_temp) {
+    LaneRegions r{};
     const size_t list_bytes = pad256((size_t)n_reads * 4);      // (the plan ids live in mat->d_plan_of)
-    const PlaceTunables& tun = mat->tun;
-    size_t sort_temp = 0;
-    HIP_TRY(sort_reads_temp_bytes(n_reads, &sort_temp));
-    sort_temp = pad256(sort_temp);
-    // sort temp of the whole-tree plan and of the four walk classes (their sorts run on different side streams)
-    constexpr uint32_t N_SORTS = 5;
-    uint8_t* const tier_of = mat->d_plan_of + plan_base;
-    uint32_t *list = nullptr, *slot_in_blk = nullptr, *key_in = nullptr, *key_out = nullptr, *val_in = nullptr;
-    uint32_t* job_n = nullptr;       // jobs of every read whose walk is cut into chunks (k_route)
-    uint32_t* wlist[2] = {nullptr, nullptr};   // the plain walk classes' reads that have events in their stream (k_route appends them)
-    uint32_t* wwlist = nullptr;                // reads with many events, a wave each (wave_kernels.hip)
-    uint32_t *b_first = nullptr, *b_clist[2] = {nullptr, nullptr}, *b_jobs[2] = {nullptr, nullptr};   // the chunked classes sized blind (k_route's tables)
-    int32_t* b_ps[2] = {nullptr, nullptr};
-    uint32_t *b_pr[2] = {nullptr, nullptr}, *b_pc[2] = {nullptr, nullptr};
-    uint32_t* const wsid = mat->d_wsid_of + plan_base;   // the window crown (index into DevMAT::wc_info) of every read routed to slot WC_SLOT
-    int32_t* root_score = nullptr;
-    void* sort_tmp = nullptr;
-    // The fixed regions, one cursor over them: run from a null base it gives the block's size, run from L.ws the pointers.
-    auto carve = [&](void* base) -> size_t {
-        size_t off = 0;
-        auto take = [&](auto*& region, size_t bytes) {
-            region = reinterpret_cast<std::remove_reference_t<decltype(region)>>((uintptr_t)base + off);
-            off += bytes;
-        };
-        take(list, list_bytes);
-        take(root_score, list_bytes);
-        take(slot_in_blk, list_bytes);
-        take(job_n, list_bytes);
-        take(wlist[0], list_bytes);
-        take(wlist[1], list_bytes);
-        take(b_first, list_bytes);
-        take(wwlist, list_bytes);
-        // (the chunked walk classes sized blind: per class its reads, its job table, three partials per job)
-        for (uint32_t cc = 0; cc < 2; cc++) {
-            take(b_clist[cc], (size_t)BLIND_CHUNKED_READS * 4);
-            take(b_jobs[cc], (size_t)BLIND_JOB_CAP * 4);
-            take(b_ps[cc], (size_t)BLIND_JOB_CAP * 4);
-            take(b_pr[cc], (size_t)BLIND_JOB_CAP * 4);
-            take(b_pc[cc], (size_t)BLIND_JOB_CAP * 4);
-        }
-        take(key_in, list_bytes);
-        take(key_out, list_bytes);
-        take(val_in, list_bytes);                 // the sorted lists (same offsets as in `list`)
-        take(sort_tmp, N_SORTS * sort_temp);
-        return off;
+    size_t off = 0;
+    auto take = [&](auto*& region, size_t bytes) {
+        region = reinterpret_cast<std::remove_reference_t<decltype(region)>>((uintptr_t)base + off);
+        off += bytes;
     };
-    {
-        // (half as much again, as ever; a device-wide synchronisation in front of the free: the lane's previous call may
-        // still run out of these regions)
-        const int rc = L.ws.reserve(carve(nullptr), 2, "workspace");
-        if (rc != WEPP_OK) return rc;
+    take(r.list, list_bytes);
+    take(r.root_score, list_bytes);
+    take(r.slot_in_blk, list_bytes);
+    take(r.job_n, list_bytes);
+    take(r.wlist[0], list_bytes);
+    take(r.wlist[1], list_bytes);
+    take(r.b_first, list_bytes);
+    take(r.wwlist, list_bytes);
+    // (the chunked walk classes sized blind: per class its reads, its job table, three partials per job)
+    for (uint32_t cc = 0; cc < 2; cc++) {
+        take(r.b_clist[cc], (size_t)BLIND_CHUNKED_READS * 4);
+        take(r.b_jobs[cc], (size_t)BLIND_JOB_CAP * 4);
+        take(r.b_ps[cc], (size_t)BLIND_JOB_CAP * 4);
+        take(r.b_pr[cc], (size_t)BLIND_JOB_CAP * 4);
+        take(r.b_pc[cc], (size_t)BLIND_JOB_CAP * 4);
     }
-    carve(L.ws.ptr);
-    uint32_t* const tier_info = L.d_info + L.info_idx * TI_WORDS;
-    uint32_t* const blk_counts = L.d_info + 2 * TI_WORDS;
+    take(r.key_in, list_bytes);
+    take(r.key_out, list_bytes);
+    take(r.val_in, list_bytes);
+    take(r.sort_tmp, N_SORTS * sort_temp);
+    r.sort_temp = sort_temp;
+    r.bytes = off;
+    return r;
+}
 
+// What is decided before the first launch of a call, from the tunables and the handle's hints (choose_form).
+struct CallForm {
+    bool walking, step_unfused, report, ext_stamps, jobs8_blind, scatter_blind, ww_jobs;
+    uint32_t report_seq, walk_limit, job_events, seed_min_hard, ev_slot;      // report_seq: the sequence number k_step reports with (report)
+    uint32_t step_group, prev_walkers, lists_hint;      // k_step's lane groups and the hints they and the next expect_lists go by
+    hipStream_t ps;                  // the plan stream
+    hipEvent_t fork_from;
+};
+
+struct PlaceCall {
+    wepp_mat_t* mat;
+    PlaceLane* L;
+    CallReads rd;
+    CallResults out;
+    uint32_t n_reads;
+    hipStream_t stream;              // the caller's
+    uint8_t* tier_of = nullptr;      // the plan id and the arena slice of every read: k_route writes both
+    uint32_t* tier_info = nullptr;   // this call's set of the lane's counters on the device (blk_counts lies behind both sets)
+    LaneRegions r{};
+    CallForm f{};
+    // what later stages need from earlier ones
+    bool scattered = false, ev1_on_step = false;     // k_scatter of this call is queued on ps; the call's second time stamp rides on k_step's launch
+    uint32_t walk_sides = 0;         // bit i: side stream i holds a walk chain, blind or late, to join into the caller's stream
+};
+
+// stage 1.  The lane's two device blocks (handle.hpp: PlaceLane).  L.ws, the fixed regions: sized by n_reads alone and
+// grown here, before k_route writes into them, so they stay where they are for the whole call.  L.part, the partials:
+// sized from the routing counters and grown behind the planner (reserve_partials), before anything of this call has
+// touched it.
+int carve_workspace(PlaceCall& c, uint32_t plan_base) {
+    PlaceLane& L = *c.L;
+    size_t sort_temp = 0;
+    HIP_TRY(sort_reads_temp_bytes(c.n_reads, &sort_temp));
+    sort_temp = pad256(sort_temp);
+    // (half as much again, as ever; a device-wide synchronisation in front of the free: the lane's previous call may
+    // still run out of these regions)
+    WEPP_TRY(L.ws.reserve(carve_lane(nullptr, c.n_reads, sort_temp).bytes, 2, "workspace"));
+    c.r = carve_lane(L.ws.ptr, c.n_reads, sort_temp);
+    c.tier_of = c.mat->d_plan_of + plan_base;
+    c.rd.root_score = c.r.root_score;
+    c.rd.wsid = c.mat->d_wsid_of + plan_base;   // the window crown (index into DevMAT::wc_info) of every read routed to slot WC_SLOT
+    c.tier_info = L.d_info + L.info_idx * TI_WORDS;
+    return WEPP_OK;
+}
+
+// stage 2.  The only reader of the handle's hints before the call; it claims the call's slot of the event ring and,
+// for a call by report, the lane's next sequence number.
+CallForm choose_form(wepp_mat_t* mat, PlaceLane& L, uint32_t n_reads, hipStream_t stream) {
+    const PlaceTunables& tun = mat->tun;
+    CallForm f{};
     // events per job of the two chunked classes: they follow the handle's traffic (device_mat.hpp: WALK_TARGET_JOBS)
-    const uint32_t job_events = mat->job_events[0] | (mat->job_events[1] << 16);
-    const uint32_t walk_max_events = tun.walk_max_events;
+    f.job_events = mat->job_events[0] | (mat->job_events[1] << 16);
     // whole-genome samples are seeded (seed_kernels.hip) when work skipping is on and the tree carries signatures
-    const uint32_t seed_min_hard = (mat->use_seeds && mat->use_crowns && mat->dev.seed_chunks) ? tun.seed_min_hard : 0xFFFFFFFFu;
-    // ---- route the reads to streams ------------------------------------------------------
-    const uint32_t ev_slot = (uint32_t)(mat->n_timed.fetch_add(1, std::memory_order_relaxed) % wepp_mat::kRing);
+    f.seed_min_hard = (mat->use_seeds && mat->use_crowns && mat->dev.seed_chunks) ? tun.seed_min_hard : 0xFFFFFFFFu;
+    f.ev_slot = (uint32_t)(mat->n_timed.fetch_add(1, std::memory_order_relaxed) % wepp_mat::kRing);
     // Streams of a call (handle.hpp: SIDE_*).  The caller's stream runs k_route and, right behind it (no cross-stream wait: ~25 us), the
     // chunked walks of the first class -- the longest chain of the common case; the plain walks and the second chunked
     // class start from the routing kernel's event on side streams; everything the HOST has to size -- the counters'
     // copy, k_scatter, the sweeps, the planned walks -- lives on the plan stream `ps`, off the walks' path.  What ran
     // there behind the copy joins the caller's stream at the end; a call that launched nothing there joins nothing.
-    const bool walking = mat->use_walk && walk_max_events;
-    hipStream_t ps = walking ? L.side[SIDE_PLAN] : stream;
+    f.walking = mat->use_walk && tun.walk_max_events;
+    f.ps = f.walking ? L.side[SIDE_PLAN] : stream;
     // WEPP_STEP_UNFUSED=1 (A/B aid): the launches behind k_route as they were before k_step -- the plain walks, k_walk_wave
     // on a side stream, the 8-entry job class blind on another, forked from an event of their own; results are identical
-    const bool step_unfused = tun.step_unfused;
+    f.step_unfused = tun.step_unfused;
     // what the side streams of a call wait for: the event behind k_route.  The timing event of the call's ring slot is
     // recorded there anyway and serves (a second record cost a call into the runtime per step).
-    const hipEvent_t fork_from = step_unfused ? L.route_ev : mat->ev0[ev_slot];
+    f.fork_from = f.step_unfused ? (hipEvent_t)L.route_ev : mat->ev0[f.ev_slot];
     // THE COUNTERS' WAY TO THE HOST.  A call with k_step has the kernel report them: its first wave copies them into the
     // lane's block of host memory and stores this call's sequence number behind them (walk_kernels.hip), the host polls
     // that word -- no second stream, no copy, no event in front of the poll.  Every other call (walks off,
     // WEPP_STEP_UNFUSED=1) and WEPP_INFO_COPY=1 (A/B aid and fallback) copy them on the plan stream and poll an event.
-    const bool report = walking && !step_unfused && !tun.info_copy && n_reads > 0;
-    uint32_t report_seq = 0;
-    if (report) report_seq = L.info_seq = info_next_seq(L.info_seq);
+    f.report = f.walking && !f.step_unfused && !tun.info_copy && n_reads > 0;
+    if (f.report) f.report_seq = L.info_seq = info_next_seq(L.info_seq);
     // THE TWO TIME STAMPS ride on the kernels' own dispatch packets: ev0 is the stop event of k_route's launch, ev1 the
     // one of k_step's -- re-recorded at the end of the call when something was joined into the caller's stream behind
     // k_step.  WEPP_STAMP_RECORDS=1 (A/B aid): two records of their own, as before.  The span means the same either way.
-    const bool ext_stamps = !tun.stamp_records;
-    bool ev1_on_step = false;
+    f.ext_stamps = !tun.stamp_records;
     // the 8-entry job class (reads with more events than a wave pass takes): launched blind behind k_route only when the
     // handle's previous call held such reads -- two launches that find nothing, a fork and a join otherwise --, else from
     // the counters like the 16-entry class.  A hint: a call it misleads launches the class late and places every read.
-    const bool jobs8_blind = step_unfused || mat->expect_jobs8.load(std::memory_order_relaxed) != 0;
+    f.jobs8_blind = f.step_unfused || mat->expect_jobs8.load(std::memory_order_relaxed) != 0;
     // k_scatter (the reads grouped by plan: `list`) is read by the launches the host plans and by nothing else -- sweeps,
     // window tiles, arena sweeps, seeds, the chunked classes it plans itself, and their sorts.  A sequencing run's batch
-    // holds none: the kernel, a pass over every read, runs only when the counters name a consumer (lists_needed below),
-    // LATE, behind the counters' copy.  A handle whose previous call had consumers launches it BLIND behind the copy, as
-    // every call did before, and loses nothing.  A hint like expect_jobs8: a call it misleads pays the late launch or an
-    // idle kernel, never a result.  Bit 0 of expect_lists = expect consumers; bit 1 = the last blind launch it asked for
-    // found none: the next call WITH consumers then does not set bit 0 again, so that batches of both kinds in turn do
-    // not pay an idle kernel and a join in front of every other one of them.  WEPP_SCATTER_BLIND=1 (A/B aid),
+    // holds none: the kernel, a pass over every read, runs only when the counters name a consumer (launch_plan.hpp:
+    // lists_needed), LATE, behind the counters' copy.  A handle whose previous call had consumers launches it BLIND behind
+    // the copy, as every call did before, and loses nothing.  A hint like expect_jobs8: a call it misleads pays the late
+    // launch or an idle kernel, never a result.  Bit 0 of expect_lists = expect consumers; bit 1 = the last blind launch
+    // it asked for found none: the next call WITH consumers then does not set bit 0 again, so that batches of both kinds
+    // in turn do not pay an idle kernel and a join in front of every other one of them.  WEPP_SCATTER_BLIND=1 (A/B aid),
     // WEPP_STEP_UNFUSED=1 and a call without walks (every read is listed, ps is the caller's stream): always blind.
-    const uint32_t lists_hint = mat->expect_lists.load(std::memory_order_relaxed);
-    const bool scatter_blind = !walking || step_unfused || tun.scatter_blind || (lists_hint & 1u) != 0;
-    bool need_lists = !walking;       // (from the counters, once the host has them)
-    bool scattered = false;           // k_scatter of this call is queued on ps
-    auto scatter = [&]() -> hipError_t {
-        scattered = true;
-        // (a call by report has put nothing on the plan stream yet: it forks here, in front of its first launch there)
-        if (report) {
-            const hipError_t e = hipStreamWaitEvent(ps, fork_from, 0);
-            if (e != hipSuccess) return e;
-        }
-        return launch_scatter(tier_of, slot_in_blk, n_reads, blk_counts, tier_info, list, walking, ps);
-    };
-    // one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
-    auto blind_class = [&](uint32_t cls, hipStream_t q) -> hipError_t {
-        if (cls == PLAN_WALK8 || cls == PLAN_WALK16) {
-            return launch_walk_blind(mat->dev, cls, cls == PLAN_WALK8 ? WALK8_ROWS : WALK16_ROWS, n_reads, wlist[cls], tier_info + TI_WCUR + cls, d_read_off, d_read_word,
-                                  root_score, d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, q);
-        }
-        const uint32_t cc = cls - PLAN_WALKC8;
-        WalkJobs jb{};
-        jb.job_first = b_first;
-        jb.skip = tier_info + TI_JOVER + cc;
-        jb.job_n = job_n;
-        jb.part_score = b_ps[cc];
-        jb.part_rank = b_pr[cc];
-        jb.part_cnt = b_pc[cc];
-        return launch_walk_jobs_blind(mat->dev, cls, cc ? WALK16_ROWS : WALK8_ROWS, jb, b_jobs[cc], tier_info + TI_JCUR + cc, b_clist[cc], tier_info + TI_CCUR + cc,
-                                      d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, q);
-    };
-    // ... on side stream i, forked from the event behind k_route and joined into the caller's stream at the end of the call
-    auto blind_side = [&](uint32_t cls, uint32_t i) -> hipError_t {
-        hipError_t e = hipStreamWaitEvent(L.side[i], fork_from, 0);
-        if (e == hipSuccess) e = blind_class(cls, L.side[i]);
-        if (e == hipSuccess) e = hipEventRecord(L.join_ev[i], L.side[i]);
-        return e;
-    };
-    const bool ww_jobs = mat->ww_by_jobs.load(std::memory_order_relaxed) != 0;     // (the reads with 17 - 256 events: a wave each, or jobs -- by the handle's previous call)
+    f.lists_hint = mat->expect_lists.load(std::memory_order_relaxed);
+    f.scatter_blind = !f.walking || f.step_unfused || tun.scatter_blind || (f.lists_hint & 1u) != 0;
+    f.ww_jobs = mat->ww_by_jobs.load(std::memory_order_relaxed) != 0;     // (the reads with 17 - 256 events: a wave each, or jobs -- by the handle's previous call)
     // (... and then reads of up to 16 events walk plainly, as before the waves: 100 000 reads with 7 - 16 events are
     // nothing to a walk launch -- its time is its longest walk -- and 0.3 ms as jobs)
-    const uint32_t walk_limit = (ww_jobs && !tun.ww_fixed) ? std::max(walk_max_events, WALK_MAX_EVENTS_BY_JOBS) : walk_max_events;
-    {
-        // the counters alternate between two sets: this call's set is zero (cleared at creation or by the
-        // previous k_route), and this k_route clears the other one for the next call
-        uint32_t* tier_info_next = L.d_info + (L.info_idx ^ 1u) * TI_WORDS;
-        // k_route places the reads that have no event in their stream itself and lists the other plain walkers; their
-        // walks are launched from those lists at once, sized for the worst case, on a side stream -- the routing
-        // counters' trip to the host, the planning of the rarer classes and k_scatter are off their path
-        RouteDirect direct{};
-        if (walking) direct = RouteDirect{{wlist[0], wlist[1]}, {b_clist[0], b_clist[1]}, {b_jobs[0], b_jobs[1]}, b_first, wwlist,
-                                          d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, walk_max_events,
-                                          tun.ww_fixed ? tun.ww_block_max_small : ww_jobs ? 0u : 0xFFFFFFFFu, tun.ww_fixed ? tun.ww_block_max_big : ww_jobs ? 0u : 0xFFFFFFFFu};
-        HIP_TRY(launch_route(mat->dev, d_read_off, d_read_word, n_reads, mat->use_crowns, walking ? walk_limit : 0u, job_events, WALK8_ROWS, WALK16_ROWS, seed_min_hard, tun.seed_min_nodes, job_n, tier_of, root_score, blk_counts,
-                             tier_info, slot_in_blk, tier_info_next, wsid, direct, stream, ext_stamps ? mat->ev0[ev_slot] : nullptr));
-        L.info_idx ^= 1u;
-        if (!ext_stamps) HIP_TRY(hipEventRecord(mat->ev0[ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
-        if (walking) {
-            if (step_unfused) HIP_TRY(hipEventRecord(L.route_ev, stream));
-            // Launched BLIND, sized for the worst case, before the routing counters are back: the plain walkers of at most
-            // WALK8_K entries -- nearly every read of a sequencing run -- and the reads with many events, a wave per 64 of them
-            // (place_dev.hpp), in ONE launch on the caller's stream, right behind k_route (no cross-stream wait: ~15 - 30 us):
-            // k_step's workgroups take their role from k_route's counters on the device.  The chunked class (reads with even
-            // more events, cut into jobs: k_route has entered them into a job table; walk + combination leave at once when
-            // the class outgrew the table, TI_JOVER: the host's planned launch takes it) goes blind on a side stream when the
-            // handle expects such reads.  The classes of 9 - 16 entries are launched from the same tables once the counters
-            // say they hold reads (blind_class below): two launches sized for a million reads that find a handful cost
-            // ~20 us of workgroup dispatch each, and eight API calls per device call.
-            if (step_unfused) {
-                HIP_TRY(blind_class(PLAN_WALK8, stream));
-                hipStream_t q = L.side[SIDE_WAVE];
-                HIP_TRY(hipStreamWaitEvent(q, fork_from, 0));
-                HIP_TRY(launch_walk_wave(mat->dev, wwlist, tier_info + TI_WWCUR, n_reads, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score, d_num_best,
-                                         d_flags, mat->d_work, wsid, q));
-                HIP_TRY(hipEventRecord(L.join_ev[SIDE_WAVE], q));
-            } else {
-                // (wwlist also takes the few walkers of 9 - 16 entries k_route moves there, TI_W16WAVE, whatever the hint
-                // ww_by_jobs says: k_step reads the lists' cursors, and is the plain blind walk when they are empty)
-                // (the walkers by lane groups as wide as the most events one of them can hold: 8 lanes for the default
-                // limit, 16 while the handle lets up to WALK_MAX_EVENTS_BY_JOBS events walk plainly; a limit beyond
-                // (WEPP_WALK_MAX_EVENTS) and WEPP_STEP_GROUPS=0 keep them lane = read)
-                // A group pass costs a wave per 64 / G walkers where lane = read costs one per 64: a batch FULL of walkers
-                // (N-rich reads, bushy trees: several hundred thousand of a million) is cheaper lane = read, so the form
-                // goes by the walkers of the handle's previous call (step_walkers; a hint like ww_by_jobs: a call it
-                // misleads costs time, never a result)
-                const bool few = mat->step_walkers.load(std::memory_order_relaxed) <= STEP_GROUPS_MAX_WALKERS;
-                const uint32_t group = (!tun.step_groups || !few || walk_limit > 16u) ? 0u : walk_limit > 8u ? 16u : 8u;
-                if (tun.debug_plans) fprintf(stderr, "[step] walkers by groups of %u lanes (0: lane = read); plain walkers of the previous call: %u\n", group, mat->step_walkers.load(std::memory_order_relaxed));
-                HIP_TRY(launch_step(mat->dev, group, WALK8_ROWS, n_reads, wlist[0], tier_info + TI_WCUR, wwlist, tier_info + TI_WWCUR, d_read_off, d_read_word, root_score,
-                                    d_best_bfs_j, d_score, d_num_best, d_flags, mat->d_work, wsid, stream,
-                                    report ? StepReport{tier_info, L.d_report, report_seq} : StepReport{nullptr, nullptr, 0u}, ext_stamps ? mat->ev1[ev_slot] : nullptr));
-                ev1_on_step = ext_stamps && n_reads > 0;      // (no reads, no launch)
-            }
-            // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
-            if (jobs8_blind) HIP_TRY(blind_side(PLAN_WALKC8, SIDE_JOBS8));
-            // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
-            // below -- a blind k_scatter may write those words while k_step reports them).  By report, k_step has them
-            // on their way as its first act and the plan stream stays empty unless k_scatter goes blind (it forks
-            // itself).  By copy, the copy goes directly behind the plan stream's wait, in front of any k_scatter, and an
-            // event of its own tells the host when it has landed -- whatever is queued behind it.  Either way the host
-            // then returns, and enqueues the next call's k_route, while k_step still runs.
-            if (!report) {
-                HIP_TRY(hipStreamWaitEvent(ps, fork_from, 0));
-                HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-                HIP_TRY(hipEventRecord(L.info_ev, ps));
-            }
-            if (scatter_blind) HIP_TRY(scatter());
-        } else {
-            // (no walks: every read is listed, on the caller's stream, the counters behind the lists as ever)
-            HIP_TRY(scatter());
-            HIP_TRY(hipMemcpyAsync(L.h_info, tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, ps));
-            HIP_TRY(hipEventRecord(L.info_ev, ps));
-        }
+    f.walk_limit = (f.ww_jobs && !tun.ww_fixed) ? std::max(tun.walk_max_events, WALK_MAX_EVENTS_BY_JOBS) : tun.walk_max_events;
+    // k_step's walkers by lane groups as wide as the most events one of them can hold: 8 lanes for the default limit, 16
+    // while the handle lets up to WALK_MAX_EVENTS_BY_JOBS events walk plainly; a limit beyond (WEPP_WALK_MAX_EVENTS) and
+    // WEPP_STEP_GROUPS=0 keep them lane = read.  A group pass costs a wave per 64 / G walkers where lane = read costs one
+    // per 64: a batch FULL of walkers (N-rich reads, bushy trees: several hundred thousand of a million) is cheaper
+    // lane = read, so the form goes by the walkers of the handle's previous call (step_walkers; a hint like ww_by_jobs:
+    // a call it misleads costs time, never a result)
+    f.prev_walkers = mat->step_walkers.load(std::memory_order_relaxed);
+    const bool few = f.prev_walkers <= STEP_GROUPS_MAX_WALKERS;
+    f.step_group = (!tun.step_groups || !few || f.walk_limit > 16u) ? 0u : f.walk_limit > 8u ? 16u : 8u;
+    return f;
+}
+
+hipError_t scatter(PlaceCall& c) {
+    c.scattered = true;
+    // (a call by report has put nothing on the plan stream yet: it forks here, in front of its first launch there)
+    if (c.f.report) {
+        const hipError_t e = hipStreamWaitEvent(c.f.ps, c.f.fork_from, 0);
+        if (e != hipSuccess) return e;
     }
-    // the host sizes the launches from the counters, and the GPU idles until it has: poll for them (a
-    // blocking wait adds its wake-up, ~15 us per call, to that idle time) ...
-    if (report) {
-        // ... the sequence word of the report block (info_wait.hpp: spinning, then yielding, and from 2 ms on asking the
-        // caller's stream now and then, so that a call whose report cannot come ends with an error instead of waiting on)
-        volatile const uint32_t* const word = L.h_info + info_seq_word(TI_WORDS);
-        const hipEvent_t step_ev = ev1_on_step ? mat->ev1[ev_slot] : nullptr;
-        const auto t_poll = std::chrono::steady_clock::now();
-        const InfoWaitResult w = wait_info_word(
-            report_seq, [&]() { return __atomic_load_n(word, __ATOMIC_ACQUIRE); },
-            [&]() {
-                const hipError_t q = step_ev ? hipEventQuery(step_ev) : hipStreamQuery(stream);
-                (void)hipGetLastError();
-                return q == hipSuccess ? 0 : q == hipErrorNotReady ? -1 : (int)q;
-            },
-            [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_poll).count(); });
-        if (w.what == InfoWait::stream_error) return hip_fail((hipError_t)w.error, "waiting for the routing counters");
-        if (w.what == InfoWait::lost) return set_error(WEPP_EDEVICE, "internal error: k_step ended without reporting the routing counters of its call");
+    return launch_scatter(c.tier_of, c.r.slot_in_blk, c.n_reads, c.L->d_info + 2 * TI_WORDS, c.tier_info, c.r.list, c.f.walking, c.f.ps);
+}
+
+// one walk class out of k_route's tables: the plain classes from their read lists, the chunked ones from their job tables
+hipError_t blind_class(const PlaceCall& c, uint32_t cls, hipStream_t q) {
+    const LaneRegions& r = c.r;
+    if (cls == PLAN_WALK8 || cls == PLAN_WALK16)
+        return launch_walk_blind(c.mat->dev, cls, cls == PLAN_WALK8 ? WALK8_ROWS : WALK16_ROWS, c.n_reads, r.wlist[cls], c.tier_info + TI_WCUR + cls, c.rd, c.out,
+                                 c.mat->d_work, q);
+    const uint32_t cc = cls - PLAN_WALKC8;
+    const WalkJobs jb{0, 0, r.b_first, c.tier_info + TI_JOVER + cc, nullptr, r.job_n, r.b_ps[cc], r.b_pr[cc], r.b_pc[cc]};   // (no list: job_first and skip instead of job_off)
+    return launch_walk_jobs_blind(c.mat->dev, cls, cc ? WALK16_ROWS : WALK8_ROWS, jb, r.b_jobs[cc], c.tier_info + TI_JCUR + cc, r.b_clist[cc], c.tier_info + TI_CCUR + cc,
+                                  c.rd, c.out, c.mat->d_work, q);
+}
+
+// ... on side stream i, forked from the event behind k_route and joined into the caller's stream at the end of the call
+hipError_t blind_side(PlaceCall& c, uint32_t cls, uint32_t i) {
+    PlaceLane& L = *c.L;
+    c.walk_sides |= 1u << i;
+    hipError_t e = hipStreamWaitEvent(L.side[i], c.f.fork_from, 0);
+    if (e == hipSuccess) e = blind_class(c, cls, L.side[i]);
+    if (e == hipSuccess) e = hipEventRecord(L.join_ev[i], L.side[i]);
+    return e;
+}
+
+// the counters' copy to the host on the plan stream, and the event that tells the host when it has landed
+int copy_counters(const PlaceCall& c) {
+    HIP_TRY(hipMemcpyAsync(c.L->h_info, c.tier_info, TI_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, c.f.ps));
+    HIP_TRY(hipEventRecord(c.L->info_ev, c.f.ps));
+    return WEPP_OK;
+}
+
+// stage 3.  Route the reads to streams and launch what goes blind.
+int route_and_launch_blind(PlaceCall& c) {
+    wepp_mat_t* mat = c.mat;
+    PlaceLane& L = *c.L;
+    const CallForm& f = c.f;
+    const LaneRegions& r = c.r;
+    const PlaceTunables& tun = mat->tun;
+    const hipStream_t stream = c.stream;
+    // the counters alternate between two sets: this call's set is zero (cleared at creation or by the
+    // previous k_route), and this k_route clears the other one for the next call
+    uint32_t* tier_info_next = L.d_info + (L.info_idx ^ 1u) * TI_WORDS;
+    // k_route places the reads that have no event in their stream itself and lists the other plain walkers; their
+    // walks are launched from those lists at once, sized for the worst case, on a side stream -- the routing
+    // counters' trip to the host, the planning of the rarer classes and k_scatter are off their path
+    RouteDirect direct{};
+    if (f.walking) direct = RouteDirect{{r.wlist[0], r.wlist[1]}, {r.b_clist[0], r.b_clist[1]}, {r.b_jobs[0], r.b_jobs[1]}, r.b_first, r.wwlist,
+                                        c.out.best_bfs_j, c.out.score, c.out.num_best, c.out.flags, mat->d_work, tun.walk_max_events,
+                                        tun.ww_fixed ? tun.ww_block_max_small : f.ww_jobs ? 0u : 0xFFFFFFFFu, tun.ww_fixed ? tun.ww_block_max_big : f.ww_jobs ? 0u : 0xFFFFFFFFu};
+    HIP_TRY(launch_route(mat->dev, c.rd.off, c.rd.word, c.n_reads, mat->use_crowns, f.walking ? f.walk_limit : 0u, f.job_events, WALK8_ROWS, WALK16_ROWS, f.seed_min_hard, tun.seed_min_nodes, r.job_n, c.tier_of, r.root_score, c.L->d_info + 2 * TI_WORDS,
+                         c.tier_info, r.slot_in_blk, tier_info_next, const_cast<uint32_t*>(c.rd.wsid), direct, stream, f.ext_stamps ? mat->ev0[f.ev_slot] : nullptr));
+    L.info_idx ^= 1u;
+    if (!f.ext_stamps) HIP_TRY(hipEventRecord(mat->ev0[f.ev_slot], stream));        // (the timed span of a call: everything behind the routing kernel)
+    if (!f.walking) {
+        // (no walks: every read is listed, on the caller's stream, the counters behind the lists as ever)
+        HIP_TRY(scatter(c));
+        return copy_counters(c);
+    }
+    if (f.step_unfused) HIP_TRY(hipEventRecord(L.route_ev, stream));
+    // Launched BLIND, sized for the worst case, before the routing counters are back: the plain walkers of at most
+    // WALK8_K entries -- nearly every read of a sequencing run -- and the reads with many events, a wave per 64 of them
+    // (place_dev.hpp), in ONE launch on the caller's stream, right behind k_route (no cross-stream wait: ~15 - 30 us):
+    // k_step's workgroups take their role from k_route's counters on the device.  The chunked class (reads with even
+    // more events, cut into jobs: k_route has entered them into a job table; walk + combination leave at once when
+    // the class outgrew the table, TI_JOVER: the host's planned launch takes it) goes blind on a side stream when the
+    // handle expects such reads.  The classes of 9 - 16 entries are launched from the same tables once the counters
+    // say they hold reads (launch_late): two launches sized for a million reads that find a handful cost
+    // ~20 us of workgroup dispatch each, and eight API calls per device call.
+    if (f.step_unfused) {
+        HIP_TRY(blind_class(c, PLAN_WALK8, stream));
+        hipStream_t q = L.side[SIDE_WAVE];
+        HIP_TRY(hipStreamWaitEvent(q, f.fork_from, 0));
+        HIP_TRY(launch_walk_wave(mat->dev, r.wwlist, c.tier_info + TI_WWCUR, c.n_reads, c.rd, c.out, mat->d_work, q));
+        HIP_TRY(hipEventRecord(L.join_ev[SIDE_WAVE], q));
+        c.walk_sides |= 1u << SIDE_WAVE;
     } else {
-        // ... spinning for the first 200 us (the routing kernel of a million reads takes ~45, behind the reads' H2D), then yielding the core
-        // between queries -- eight ranks spinning on the cores of one container starve their own staging workers --,
-        // and after ~2 ms (a long queue in front of this call) waiting blocking
-        hipError_t q = hipErrorNotReady;
-        const auto t_poll = std::chrono::steady_clock::now();
-        for (;;) {
-            q = hipEventQuery(L.info_ev);
-            if (q != hipErrorNotReady) break;
-            const auto waited = std::chrono::steady_clock::now() - t_poll;
-            if (waited > std::chrono::milliseconds(2)) break;
-            if (waited > std::chrono::microseconds(200)) std::this_thread::yield();
-        }
-        (void)hipGetLastError();   // "not ready" is not an error: keep it out of the launchers' hipGetLastError()
-        if (q != hipSuccess) HIP_TRY(hipEventSynchronize(L.info_ev));
+        // (wwlist also takes the few walkers of 9 - 16 entries k_route moves there, TI_W16WAVE, whatever the hint
+        // ww_by_jobs says: k_step reads the lists' cursors, and is the plain blind walk when they are empty)
+        // (the walkers by lane groups or lane = read: choose_form)
+        if (tun.debug_plans) fprintf(stderr, "[step] walkers by groups of %u lanes (0: lane = read); plain walkers of the previous call: %u\n", f.step_group, f.prev_walkers);
+        HIP_TRY(launch_step(mat->dev, f.step_group, WALK8_ROWS, c.n_reads, r.wlist[0], c.tier_info + TI_WCUR, r.wwlist, c.tier_info + TI_WWCUR, c.rd, c.out, mat->d_work, stream,
+                            f.report ? StepReport{c.tier_info, L.d_report, f.report_seq} : StepReport{nullptr, nullptr, 0u}, f.ext_stamps ? mat->ev1[f.ev_slot] : nullptr));
+        c.ev1_on_step = f.ext_stamps && c.n_reads > 0;      // (no reads, no launch)
     }
-    if (walking) {
+    // (the job class on a stream of its own: ~10 us that would sit behind the walks on the call's longest chain)
+    if (f.jobs8_blind) HIP_TRY(blind_side(c, PLAN_WALKC8, SIDE_JOBS8));
+    // COUNTERS FIRST: they are final when k_route ends (k_scatter adds only TI_OFF, which the host forms itself
+    // in wait_counters -- a blind k_scatter may write those words while k_step reports them).  By report, k_step has
+    // them on their way as its first act and the plan stream stays empty unless k_scatter goes blind (it forks
+    // itself).  By copy, the copy goes directly behind the plan stream's wait, in front of any k_scatter, and an
+    // event of its own tells the host when it has landed -- whatever is queued behind it.  Either way the host
+    // then returns, and enqueues the next call's k_route, while k_step still runs.
+    if (!f.report) {
+        HIP_TRY(hipStreamWaitEvent(f.ps, f.fork_from, 0));
+        WEPP_TRY(copy_counters(c));
+    }
+    if (f.scatter_blind) HIP_TRY(scatter(c));
+    return WEPP_OK;
+}
+
+// The wait by report: the sequence word of the report block (info_wait.hpp: spinning, then yielding, and from 2 ms on
+// asking the caller's stream now and then, so that a call whose report cannot come ends with an error instead of
+// waiting on)
+int wait_report(const PlaceCall& c) {
+    volatile const uint32_t* const word = c.L->h_info + info_seq_word(TI_WORDS);
+    const hipEvent_t step_ev = c.ev1_on_step ? c.mat->ev1[c.f.ev_slot] : nullptr;
+    const hipStream_t stream = c.stream;
+    const auto t_poll = std::chrono::steady_clock::now();
+    const InfoWaitResult w = wait_info_word(
+        c.f.report_seq, [&]() { return __atomic_load_n(word, __ATOMIC_ACQUIRE); },
+        [&]() {
+            const hipError_t q = step_ev ? hipEventQuery(step_ev) : hipStreamQuery(stream);
+            (void)hipGetLastError();
+            return q == hipSuccess ? 0 : q == hipErrorNotReady ? -1 : (int)q;
+        },
+        [&]() { return (uint64_t)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t_poll).count(); });
+    if (w.what == InfoWait::stream_error) return hip_fail((hipError_t)w.error, "waiting for the routing counters");
+    if (w.what == InfoWait::lost) return set_error(WEPP_EDEVICE, "internal error: k_step ended without reporting the routing counters of its call");
+    return WEPP_OK;
+}
+
+// The wait by copy: the event behind it, spinning for the first 200 us (the routing kernel of a million reads takes ~45,
+// behind the reads' H2D), then yielding the core between queries -- eight ranks spinning on the cores of one container
+// starve their own staging workers --, and after ~2 ms (a long queue in front of this call) waiting blocking
+int wait_copy(const PlaceCall& c) {
+    hipError_t q = hipErrorNotReady;
+    const auto t_poll = std::chrono::steady_clock::now();
+    for (;;) {
+        q = hipEventQuery(c.L->info_ev);
+        if (q != hipErrorNotReady) break;
+        const auto waited = std::chrono::steady_clock::now() - t_poll;
+        if (waited > std::chrono::milliseconds(2)) break;
+        if (waited > std::chrono::microseconds(200)) std::this_thread::yield();
+    }
+    (void)hipGetLastError();   // "not ready" is not an error: keep it out of the launchers' hipGetLastError()
+    if (q != hipSuccess) HIP_TRY(hipEventSynchronize(c.L->info_ev));
+    return WEPP_OK;
+}
+
+// stage 4.  The host sizes the launches from the counters, and the GPU idles until it has: poll for them (a blocking
+// wait adds its wake-up, ~15 us per call, to that idle time).
+int wait_counters(PlaceCall& c) {
+    PlaceLane& L = *c.L;
+    WEPP_TRY(c.f.report ? wait_report(c) : wait_copy(c));
+    if (c.f.walking) {
         // TI_OFF = the exclusive prefix sum of TI_COUNT, and the total behind the last plan: what k_scatter writes on
         // the device, formed here because the copy no longer waits for it (the copy has landed: h_info is the host's)
         uint32_t off = 0;
@@ -704,35 +740,47 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
         L.h_info[TI_OFF + MAX_PLANS] = off;
     }
     const uint32_t* info = L.h_info;
-    if (tun.debug_plans) fprintf(stderr, "[info] counters by %s, lane %u, sequence %u\n", report ? "report" : "copy", lane_idx, report_seq);
-    if (tun.debug_plans)
-        fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
-                n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
-                info[TI_CCUR + 1], info[TI_JCUR], info[TI_JCUR + 1], info[TI_JOVER], info[TI_JOVER + 1]);
-    // Who reads `list`: decided HERE, from the counters, for the whole call.  A plan with reads is a consumer unless its
-    // class is placed out of k_route's own tables: the plain walk classes always, a chunked class that fitted its blind
-    // tables (TI_JOVER == 0: launched blind or from the counters below, never by a plan of the host).
-    auto lists_needed = [&]() {
-        for (uint32_t id = 0; id < MAX_PLANS; id++) {
-            if (!info[TI_COUNT + id]) continue;
-            const uint32_t cls = plan_class(id);
-            if (cls == PLAN_WALK8 || cls == PLAN_WALK16) continue;
-            if ((cls == PLAN_WALKC8 || cls == PLAN_WALKC16) && !info[TI_JOVER + (cls - PLAN_WALKC8)]) continue;
-            return true;
-        }
-        return false;
-    };
+    if (!c.mat->tun.debug_plans) return WEPP_OK;
+    fprintf(stderr, "[info] counters by %s, lane %u, sequence %u\n", c.f.report ? "report" : "copy", (uint32_t)(c.L - c.mat->lane), c.f.report_seq);
+    fprintf(stderr, "[route] reads=%u resolved=%u walk=%u,%u wave=%u,%u (of them walkers of 9 - 16 entries: %u) job reads=%u,%u jobs=%u,%u left to the host=%u,%u\n",
+            c.n_reads, info[TI_RESOLVED], info[TI_WCUR], info[TI_WCUR + 1], info[TI_WWCUR], info[TI_WWCUR + 1], info[TI_W16WAVE], info[TI_CCUR],
+            info[TI_CCUR + 1], info[TI_JCUR], info[TI_JCUR + 1], info[TI_JOVER], info[TI_JOVER + 1]);
+    return WEPP_OK;
+}
+
+// stage 5.  The hints of the handle's next call, from this call's counters (they choose how a call cuts its work, never
+// its results).  need_lists: a launch of this call reads the grouped read list.
+void store_hints(const PlaceCall& c, bool need_lists) {
+    wepp_mat_t* mat = c.mat;
+    const uint32_t* info = c.L->h_info;
+    if (c.f.walking) {
+        // (see choose_form: scatter_blind)
+        mat->expect_lists.store(need_lists ? ((c.f.lists_hint & 2u) ? 0u : 1u) : ((c.f.lists_hint & 1u) ? 2u : (c.f.lists_hint & 2u)), std::memory_order_relaxed);
+        // the 8-entry job class is launched blind when this call held such reads
+        mat->expect_jobs8.store(info[TI_CCUR] && !info[TI_JOVER] ? 1u : 0u, std::memory_order_relaxed);
+    }
+    for (uint32_t cc = 0; cc < 2; cc++) {
+        const uint64_t ev = (uint64_t)info[TI_EVENTS + cc] << 6;
+        const uint32_t je = (uint32_t)std::min<uint64_t>(WALK_JOB_EVENTS_MAX, std::max<uint64_t>(WALK_JOB_EVENTS, ev / WALK_TARGET_JOBS));
+        mat->job_events[cc] = je <= WALK_JOB_EVENTS ? je : ((je + 15u) & ~15u);       // (what the NEXT call's k_route cuts this class's walks into)
+    }
+    // the reads with 17 - 256 events of the NEXT call: a wave per 64 events each while they are few (scaled to the call's size)
+    const uint64_t scale = std::max<uint64_t>(1, ((uint64_t)c.n_reads + (1u << 20) - 1) >> 20);
+    mat->ww_by_jobs.store((info[TI_WWCAND] > WW_CALL_MAX_SMALL * scale || info[TI_WWCAND + 1] > WW_CALL_MAX_BIG * scale) ? 1u : 0u, std::memory_order_relaxed);
+    mat->step_walkers.store(info[TI_WCUR], std::memory_order_relaxed);      // (how the NEXT call's k_step places its plain walkers)
+}
+
+// stage 6.  What is launched from the counters.  k_scatter LATE: the hint said no and the counters say yes.  On ps, behind
+// the copy and in front of everything that reads the lists (all of it is launched by the stages below, on ps or on
+// streams forked from it).  Then the walk classes (joined into the caller's stream by join_and_account): the 8-entry job
+// class when the hint did not expect it, and the classes of 9 - 16 entries, from k_route's tables like the others, when
+// they hold reads.
+int launch_late(PlaceCall& c, bool need_lists) {
+    const uint32_t* info = c.L->h_info;
     const char* scatter_mode = "blind";
-    if (walking) {
-        need_lists = lists_needed();
-        // (the hint of the next call: see lists_hint above)
-        mat->expect_lists.store(need_lists ? ((lists_hint & 2u) ? 0u : 1u) : ((lists_hint & 1u) ? 2u : (lists_hint & 2u)), std::memory_order_relaxed);
-        if (!scattered) {
-            scatter_mode = need_lists ? "late" : "none";
-            // LATE: the hint said no and the counters say yes.  On ps, behind the copy and in front of everything that
-            // reads the lists (all of it is launched below, on ps or on streams forked from it).
-            if (need_lists) HIP_TRY(scatter());
-        }
+    if (c.f.walking && !c.scattered) {
+        scatter_mode = need_lists ? "late" : "none";
+        if (need_lists) HIP_TRY(scatter(c));
     }
     // Hazards of a call WITHOUT k_scatter (scattered == false from here on): nothing of this call reads blk_counts,
     // tier_of's slots or slot_in_blk -- per lane, rewritten by the lane's next k_route -- and nothing runs on ps -- by
@@ -740,422 +788,310 @@ int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_
     // this call's counter set (its two cursors; all of it for the report) on the caller's stream, in front of the next
     // k_route, which clears the OTHER set; the set after that clears this one, behind everything this call put on the caller's stream.  A k_scatter that was launched, blind or late,
     // reads those per-lane buffers and writes TI_OFF into this call's set: it and every consumer behind it are joined
-    // into the caller's stream below, before the call returns.
-    if (tun.debug_plans) fprintf(stderr, "[lists] scatter=%s plan stream joined=%d\n", scatter_mode, (int)(walking && scattered));
-    for (uint32_t cc = 0; cc < 2; cc++) {
-        const uint64_t ev = (uint64_t)info[TI_EVENTS + cc] << 6;
-        const uint32_t je = (uint32_t)std::min<uint64_t>(WALK_JOB_EVENTS_MAX, std::max<uint64_t>(WALK_JOB_EVENTS, ev / WALK_TARGET_JOBS));
-        mat->job_events[cc] = je <= WALK_JOB_EVENTS ? je : ((je + 15u) & ~15u);       // (what the NEXT call's k_route cuts this class's walks into)
-    }
+    // into the caller's stream by join_and_account, before the call returns.
+    if (c.mat->tun.debug_plans) fprintf(stderr, "[lists] scatter=%s plan stream joined=%d\n", scatter_mode, (int)(c.f.walking && c.scattered));
+    if (!c.f.walking) return WEPP_OK;
+    if (info[TI_CCUR] && !info[TI_JOVER] && !c.f.jobs8_blind) HIP_TRY(blind_side(c, PLAN_WALKC8, SIDE_JOBS8));
+    if (info[TI_WCUR + 1]) HIP_TRY(blind_side(c, PLAN_WALK16, SIDE_WALK16));
+    if (info[TI_CCUR + 1] && !info[TI_JOVER + 1]) HIP_TRY(blind_side(c, PLAN_WALKC16, SIDE_JOBS16));
+    return WEPP_OK;
+}
 
-    // the reads with 17 - 256 events of the NEXT call: a wave per 64 events each while they are few (scaled to the call's size)
-    {
-        const uint64_t scale = std::max<uint64_t>(1, ((uint64_t)n_reads + (1u << 20) - 1) >> 20);
-        mat->ww_by_jobs.store((info[TI_WWCAND] > WW_CALL_MAX_SMALL * scale || info[TI_WWCAND + 1] > WW_CALL_MAX_BIG * scale) ? 1u : 0u, std::memory_order_relaxed);
-    }
-    mat->step_walkers.store(info[TI_WCUR], std::memory_order_relaxed);      // (how the NEXT call's k_step places its plain walkers)
-    bool late16[2] = {false, false}, late8 = false;
-    if (walking) {
-        // (the walks launched behind k_route are joined into the caller's stream below)
-        // the 8-entry job class when the hint did not expect it, and the hint of the next call
-        const bool jobs8 = info[TI_CCUR] && !info[TI_JOVER];
-        if (jobs8 && !jobs8_blind) { HIP_TRY(blind_side(PLAN_WALKC8, SIDE_JOBS8)); late8 = true; }
-        mat->expect_jobs8.store(jobs8 ? 1u : 0u, std::memory_order_relaxed);
-        // the classes of 9 - 16 entries, from k_route's tables like the others, when they hold reads
-        if (info[TI_WCUR + 1]) { HIP_TRY(blind_side(PLAN_WALK16, SIDE_WALK16)); late16[0] = true; }
-        if (info[TI_CCUR + 1] && !info[TI_JOVER + 1]) { HIP_TRY(blind_side(PLAN_WALKC16, SIDE_JOBS16)); late16[1] = true; }
-    }
-    // ---- plan the launches ---------------------------------------------------------
-    struct Plan { uint32_t t, count, off, T, ntiles, nchunks, bpc, ent_cap, key_cap, lds_bytes; bool s_in_lds, dense, window, win_table; size_t part_off; const uint32_t* lst; const DevStream* st; uint64_t sbytes; };
-    Plan plans[MAX_PLANS];
-    uint32_t np = 0;
-    size_t part_total = 0;
-    const uint32_t bm_bytes = mat->dev.bm_words * 4;
-    if (bm_bytes > 128 * 1024) return set_error(WEPP_ELIMIT, "position bitmap does not fit in LDS");
-    // walk plans (device_mat.hpp): the reads of one (class, stream) that walk their own events
-    WalkPlans walkc[2]{};
-    uint32_t walkc_off[2] = {0, 0};   // list offsets of the chunked walk plans
-    uint64_t walk_reads = (uint64_t)info[TI_WCUR] + info[TI_WCUR + 1] + info[TI_RESOLVED] + info[TI_W16WAVE], n_jobs[2] = {0, 0};     // (the plain walk classes: placed by k_route itself or by the blind walks behind it)
-    uint32_t walkc_reads[2] = {0, 0};
-    uint32_t arena_n = 0, arena_off = 0, arena_maxk = 1;
-    uint32_t seed_n = 0, seed_off = 0, seed_maxk = 1;
-    size_t arena_part = 0;
-    // the window plans share ONE launch (k_sweep_windows): their chunks are sized for the tiles of all of them together
-    // (sized per plan, each window asked for enough waves to fill the chip on its own: 1.2 kb reads, 30 windows -- 9
-    // workgroups per tile, each rebuilding the tile's table to sweep two blocks of the window's stream)
-    const bool fuse_windows = mat->d_wstreams != nullptr;
-    // the tile rule.  Reads per tile: at most MAX_TILE_ENTRIES read words per tile (long reads share a sweep between
-    // fewer reads), a power of two, never more than the knob; long reads take the dense (table) variant of the sweep
-    auto tile_reads = [&](uint32_t maxk) { uint32_t Tp = T; while (Tp > 1 && (uint64_t)Tp * maxk > MAX_TILE_ENTRIES) Tp >>= 1; return Tp; };
-    auto takes_table = [&](uint32_t maxk) { return maxk <= MAX_TILE_ENTRIES && maxk >= DENSE_MIN_READ_WORDS && mat->dev.max_pos < DENSE_MAX_POS; };
-    uint64_t win_tiles = 0;
-    if (fuse_windows)
-        for (uint32_t id = 0; id < MAX_PLANS; id++) {
-            const uint32_t count = info[TI_COUNT + id], maxk = std::max<uint32_t>(1, info[TI_MAXK + id]);
-            if (count && plan_class(id) == PLAN_WIN && takes_table(maxk)) win_tiles += (count + tile_reads(maxk) - 1) / tile_reads(maxk);
-        }
-    for (uint32_t id = 0; id < MAX_PLANS; id++) {
-        const uint32_t count = info[TI_COUNT + id];
-        if (!count) continue;
-        const uint32_t t = plan_index(id), cls = plan_class(id);
-        if (cls == PLAN_SEED) {
-            // whole-genome samples: a workgroup each, final results written by the kernel (seed_kernels.hip)
-            if (!mat->dev.seed_chunks) return set_error(WEPP_EDEVICE, "routing produced an invalid plan id");
-            seed_n = count;
-            seed_off = info[TI_OFF + id];
-            seed_maxk = std::max<uint32_t>(1, info[TI_MAXK + id]);
-            continue;
-        }
-        {
-            // (slot WC_SLOT of a walk class = the window crowns: one plan, a crown per read)
-            if (cls > PLAN_WIN || (cls == PLAN_WIN ? t >= mat->wstreams.size() : (t >= ns && !(t == WC_SLOT && mat->dev.wc_windows))))
-                return set_error(WEPP_EDEVICE, "routing produced an invalid plan id");
-        }
-        if (cls == PLAN_WALKC8 || cls == PLAN_WALKC16) {
-            // the reads with many events: their walks are cut into jobs (below); the plans of a chunked class
-            // are the streams, the jobs of stream t numbered behind those of the streams before it
-            const uint32_t cc = cls - PLAN_WALKC8;
-            if (walking && !info[TI_JOVER + cc]) { walk_reads += count; continue; }     // (launched blind behind k_route)
-            WalkPlans& wc = walkc[cc];
-            WalkPlanDev& d = wc.p[wc.n];
-            d.tier = t;
-            d.n_list = info[TI_JOBS + cc * MAX_STREAMS + t];
-            d.job0 = (uint32_t)n_jobs[cc];
-            walkc_off[cc] = info[TI_OFF + plan_id(cls, 0)];
-            d.list = list + walkc_off[cc];
-            d.wave_end = (wc.n ? wc.p[wc.n - 1].wave_end : 0u) + walk_plan_waves(d.n_list);
-            wc.n++;
-            n_jobs[cc] += d.n_list;
-            walkc_reads[cc] += count;
-            walk_reads += count;
-            continue;
-        }
-        if (cls == PLAN_WALK8 || cls == PLAN_WALK16) continue;     // (never counted: k_route places or lists them itself, see walk_reads below)
-        if (cls == PLAN_SWEEP && t == WC_SLOT) {
-            // the reads that sweep their window crown, one wave each (k_sweep_arena); one partial per read
-            arena_n = count;
-            arena_off = info[TI_OFF + id];
-            arena_maxk = std::max<uint32_t>(1, info[TI_MAXK + id]);
-            arena_part = part_total;
-            part_total += (size_t)count * 12 * ARENA_CHUNKS;
-            if ((uint64_t)count * ARENA_CHUNKS >= (1ull << 31)) return set_error(WEPP_ELIMIT, "too many window-crown sweeps in one call; split the batch");
-            continue;
-        }
-        Plan& p = plans[np++];
-        p.window = cls == PLAN_WIN;
-        p.t = p.window ? ns - 1 : t;                 // (a window stream is the whole tree for its reads)
-        p.st = p.window ? &mat->wstreams[t] : &mat->streams[t];
-        p.sbytes = p.window ? mat->wstream_bytes[t] : mat->stream_bytes[t];
-        p.count = count;
-        p.off = info[TI_OFF + id];
-        const uint32_t maxk = std::max<uint32_t>(1, info[TI_MAXK + id]);
-        const uint32_t Tp = tile_reads(maxk);
-        p.T = Tp;
-        p.ntiles = (count + Tp - 1) / Tp;
-        // a read longer than MAX_TILE_ENTRIES words is swept alone with its words left in global memory
-        p.s_in_lds = maxk <= MAX_TILE_ENTRIES;
-        p.dense = takes_table(maxk);
-        const uint64_t need = std::min<uint64_t>((uint64_t)std::min(Tp, count) * maxk, MAX_TILE_ENTRIES);
-        const uint32_t cap = (uint32_t)((need + 63) & ~63ull);
-        uint32_t kcap = 64;
-        while (kcap < need) kcap <<= 1;                        // the bitonic network wants a power of two
-        p.ent_cap = p.s_in_lds ? cap : 0;
-        p.key_cap = p.dense ? kcap : 0;
-        // long reads inside a window: per-position read masks instead of sorted keys (the argument then
-        // carries the window's first position)
-        p.win_table = p.window && p.dense;
-        if (p.win_table) p.key_cap = t * WIN_STRIDE;
-        p.lds_bytes = p.s_in_lds ? sweep_lds_bytes(mat->dev.bm_words, cap, kcap, p.dense, p.win_table) : bm_bytes;
-        // chunks: enough single-wave workgroups to fill 256 CUs, cut at checkpoints
-        const DevStream& st = *p.st;
-        uint32_t nchunks = std::max<uint32_t>(1, ((p.dense ? SWEEP_TARGET_WAVES_DENSE : SWEEP_TARGET_WAVES) + p.ntiles - 1) / p.ntiles);
-        if (p.win_table && fuse_windows) nchunks = std::max<uint32_t>(1, (uint32_t)((SWEEP_TARGET_WAVES_DENSE + win_tiles - 1) / win_tiles));
-        // ... and chunks no longer than what stays in an XCD's L2 while the tiles sweep it: the waves of
-        // a launch are ordered chunk-major (all tiles of chunk 0, then of chunk 1, ...), so the ~4 K
-        // resident waves walk the same ~1.5 MB of the stream together instead of drifting apart over
-        // 118 MB (whole-tree sweep of 1 M reads: 432 ms with one chunk per tile, 235 ms with 80)
-        nchunks = std::max<uint32_t>(nchunks, (uint32_t)((p.sbytes + SWEEP_CHUNK_BYTES - 1) / SWEEP_CHUNK_BYTES));
-        nchunks = std::min<uint32_t>(nchunks, (uint32_t)std::max<uint64_t>(1, SWEEP_MAX_PARTIAL_BYTES / ((uint64_t)count * 12)));
-        // ... but a chunk's wave pays a set-up (bitmap, read words, checkpoint) worth several blocks: no chunk
-        // shorter than 8 blocks, however few tiles the plan has (a plan of a few hundred reads used to be cut into
-        // 4096 waves of one or two blocks each)
-        nchunks = std::min<uint32_t>(nchunks, std::max<uint32_t>(1, st.NB / 8));
-        if (p.dense) nchunks = std::max<uint32_t>(nchunks, DENSE_WAVES_PER_WG);   // one chunk per wave of the workgroup
-        nchunks = std::min(nchunks, st.ncp);
-        const uint32_t cps_per_chunk = (st.ncp + nchunks - 1) / nchunks;
-        p.bpc = cps_per_chunk * st.cp_stride;
-        p.nchunks = (st.NB + p.bpc - 1) / p.bpc;
-        if (p.dense) p.nchunks = (p.nchunks + DENSE_WAVES_PER_WG - 1) / DENSE_WAVES_PER_WG * DENSE_WAVES_PER_WG;
-        p.part_off = part_total;
-        part_total += (size_t)p.nchunks * count * 12;
-    }
-    if (n_jobs[0] + n_jobs[1] >= (1ull << 31)) return set_error(WEPP_ELIMIT, "too many walk jobs in one call; split the batch");
-    // ---- the lane's second block: the plans' partials and, behind them, what a chunked class the host plans itself
-    // needs -- jobs per read, their scan, the scan's scratch, three partials per job.  Nothing of this call has touched
-    // it; what the lane's previous call left running in it is waited for only when the block has to grow. ----
-    size_t scan_temp[2] = {0, 0}, walkc_base[2] = {0, 0}, part_need = pad256(part_total);
-    for (uint32_t cc = 0; cc < 2; cc++) {
-        if (!walkc[cc].n) continue;
-        HIP_TRY(scan_u32_temp_bytes(walkc_reads[cc], &scan_temp[cc]));
-        walkc_base[cc] = part_need;
-        part_need += 2 * pad256((size_t)walkc_reads[cc] * 4) + pad256(scan_temp[cc]) + 3 * pad256((size_t)n_jobs[cc] * 4);
-    }
-    {
-        // (half as much again: the partials of a batch of long reads vary by a third with the tile size its longest
-        // read allows, and a regrowth costs a hipFree + hipMalloc of ~100 MB, 16 ms)
-        const int rc = L.part.reserve(part_need, 2, "partials");
-        if (rc != WEPP_OK) return rc;
-    }
-    if (!scattered && (np || arena_n || seed_n || walkc[0].n || walkc[1].n)) return set_error(WEPP_EDEVICE, "a planned launch without its read list");
-    char* const part_base = (char*)L.part.ptr;
-    const bool debug_plans = tun.debug_plans;
-    for (uint32_t i = 0; i < np; i++) {
-        Plan& p = plans[i];
-        p.lst = list + p.off;
-        if (debug_plans)
-            fprintf(stderr, "[plan] %s t=%u count=%u off=%u T=%u ntiles=%u nchunks=%u bpc=%u NB=%u ncp=%u dense=%d lds=%u ent_cap=%u key_cap=%u part_off=%zu\n",
-                    p.window ? "window" : "sweep", p.t, p.count, p.off, p.T, p.ntiles, p.nchunks, p.bpc, p.st->NB, p.st->ncp, (int)p.dense,
-                    p.lds_bytes, p.ent_cap, p.key_cap, p.part_off);
-        // the reads that sweep the whole tree go by first listed position (sort_reads.hip)
-        if (!p.window && p.t + 1 == ns && p.count >= SORT_MIN_READS) {
-            HIP_TRY(launch_first_pos(list + p.off, p.count, d_read_off, d_read_word, key_in + p.off, ps));
-            HIP_TRY(launch_sort_reads(key_in + p.off, key_out + p.off, list + p.off, val_in + p.off, p.count, sort_tmp, sort_temp, ps));
-            p.lst = val_in + p.off;
-        }
-    }
+// ---- stage 8: the plans' launches.  What the chains share: the plan, the lists its tile plans read, the lane's
+// second block, and which side streams hold a chain to join. ----
+struct PlanLaunch : LaunchPlan {    // the plan, and what launching it adds
+    char* part_base;
+    size_t scan_temp[2], walkc_base[2];
+    bool fork;
+    uint32_t joins[MAX_STREAMS], n_joins;
+};
+struct Partials { int32_t* score; uint32_t *rank, *cnt; };
+// the three partial arrays of n (chunk, read) pairs at part_off of the lane's second block
+Partials parts(const PlanLaunch& pl, size_t part_off, size_t n) {
+    int32_t* const score = (int32_t*)(pl.part_base + part_off);
+    return Partials{score, (uint32_t*)(score + n), (uint32_t*)(score + n) + n};
+}
+const DevStream& stream_of(const wepp_mat_t* mat, const TilePlan& p) { return p.window ? mat->wstreams[p.sid] : mat->streams[p.sid]; }
 
-    // ---- sweeps (timed as a group) + finalizes ------------------------------------------
-    // The plain (short-read) plans are fused into ONE launch, longest chunks first; dense
-    // and out-of-LDS plans get their own launch on a side stream forked from / joined into
-    // `stream`.  Every plan's finalize follows its sweep.
-    uint64_t passes = 0, bytes = 0;
-    auto parts = [&](const Plan& p, int32_t*& ps, uint32_t*& pr, uint32_t*& pc) {
-        ps = (int32_t*)(part_base + p.part_off);
-        pr = (uint32_t*)(ps + (size_t)p.nchunks * p.count);
-        pc = pr + (size_t)p.nchunks * p.count;
-    };
-    uint32_t order[MAX_PLANS], n_plain = 0, n_other = 0, others[MAX_PLANS];
-    uint32_t wins[MAX_WINDOWS], n_wins = 0;
-    for (uint32_t i = 0; i < np; i++) {
-        if (plans[i].s_in_lds && !plans[i].dense && n_plain < MAX_STREAMS) order[n_plain++] = i;
-        else if (plans[i].win_table && fuse_windows && n_wins < MAX_WINDOWS) wins[n_wins++] = i;
-        else others[n_other++] = i;
-        passes += plans[i].ntiles;                                   // every tile sweeps its stream once
-        bytes += (uint64_t)plans[i].ntiles * plans[i].sbytes;
+// The lane's second block: the plans' partials and, behind them, what a chunked class the host plans itself
+// needs -- jobs per read, their scan, the scan's scratch, three partials per job.  Nothing of this call has touched
+// it; what the lane's previous call left running in it is waited for only when the block has to grow.
+int reserve_partials(const PlaceCall& c, PlanLaunch& pl) {
+    size_t part_need = pad256(pl.part_total);
+    for (uint32_t cc = 0; cc < 2; cc++) {
+        pl.scan_temp[cc] = pl.walkc_base[cc] = 0;
+        if (!pl.walkc[cc].n) continue;
+        HIP_TRY(scan_u32_temp_bytes(pl.walkc_reads[cc], &pl.scan_temp[cc]));
+        pl.walkc_base[cc] = part_need;
+        part_need += 2 * pad256((size_t)pl.walkc_reads[cc] * 4) + pad256(pl.scan_temp[cc]) + 3 * pad256((size_t)pl.n_jobs[cc] * 4);
     }
-    std::sort(order, order + n_plain, [&](uint32_t a, uint32_t b) { return plans[a].bpc > plans[b].bpc; });
-    const bool walks = walkc[0].n || walkc[1].n;
-    for (uint32_t cls = 0; cls < 2; cls++)
-        passes += (info[TI_WCUR + cls] + 63) / 64;      // a walk "pass" = one wave of 64 reads
-    passes += (info[TI_RESOLVED] + 63) / 64 + info[TI_WWCUR] + info[TI_WWCUR + 1];
-    for (uint32_t cc = 0; cc < 2; cc++)
-        if (walking && !info[TI_JOVER + cc]) {
-            passes += (info[TI_JCUR + cc] + 63) / 64;
-            bytes += (uint64_t)info[TI_CCUR + cc] * 40 + (uint64_t)info[TI_JCUR + cc] * 16;      // (job table, partials, the combination's reads and results)
-        }
-    for (uint32_t cc = 0; cc < 2; cc++)
-        if (walkc[cc].n) passes += walkc[cc].p[walkc[cc].n - 1].wave_end;
-    const uint32_t n_walk_chains = (walkc[0].n || walkc[1].n) ? 1u : 0u;
-    const uint32_t n_chains = n_other + n_walk_chains + (arena_n ? 1u : 0u) + (seed_n ? 1u : 0u) + (n_wins ? 1u : 0u);     // launch chains beside the fused plain sweeps
-    const bool fork = (n_chains > 0) && (n_plain > 0 || n_chains > 1);
-    if (fork) HIP_TRY(hipEventRecord(L.fork_ev, ps));
-    // A chain beside the fused sweeps runs on side stream i (handle.hpp: SIDE_*) when the call forks, else on ps.
-    // The side streams join ps only after everything has been launched: a join in between would make the launches
-    // behind it wait for the side stream's kernels.  join(): the chain's last launch is queued; its stream is listed once.
-    uint32_t joins[MAX_STREAMS], n_joins = 0;
-    auto fork_to = [&](uint32_t i, hipStream_t& q) -> hipError_t {
-        q = fork ? L.side[i] : ps;
-        return fork ? hipStreamWaitEvent(q, L.fork_ev, 0) : hipSuccess;
-    };
-    auto join = [&](uint32_t i) -> hipError_t {
-        if (!fork) return hipSuccess;
-        const hipError_t e = hipEventRecord(L.join_ev[i], L.side[i]);
-        if (e == hipSuccess && std::find(joins, joins + n_joins, i) == joins + n_joins) joins[n_joins++] = i;
-        return e;
-    };
-    // A walk class's reads go by (stream, first listed position) when there are enough of them (device_mat.hpp:
-    // WALK_SORT_MIN_READS): sorted on the class's own stream, right before its launch.
-    // `region` = which of the sort temp regions (1..4; 0 is the whole-tree plan's).
-    auto sort_class = [&](uint32_t cls, uint32_t region, hipStream_t q, bool& sorted) -> int {
-        sorted = false;
-        const uint32_t off = info[TI_OFF + plan_id(cls, 0)];
-        const uint32_t cnt = info[TI_OFF + plan_id(cls, 0) + MAX_STREAMS] - off;      // (plan ids of a class are consecutive)
-        if (cnt < WALK_SORT_MIN_READS) return WEPP_OK;
-        HIP_TRY(launch_walk_keys(list + off, cnt, tier_of, d_read_off, d_read_word, key_in + off, q));
-        HIP_TRY(launch_sort_reads(key_in + off, key_out + off, list + off, val_in + off, cnt, (char*)sort_tmp + region * sort_temp,
-                                  sort_temp, q, WALK_SORT_KEY_BITS));
-        sorted = true;
-        return WEPP_OK;
-    };
-    if (walks) {
-        // the walks write the final per-read results themselves; the plain ones, the chunked ones and the
-        // sweeps run side by side (the walks wait on memory most of the time)
-        hipStream_t q = ps;
-        if (walkc[0].n || walkc[1].n) {
-            // chunked walks, per class: jobs per read in list order -> exclusive scan -> the walk (a partial per
-            // job; a job finds its read by bisection in the scanned offsets) -> one combination per read.
-            // Buffers: each class's share of the lane's second block, behind the plans' partials (walkc_base above).
-            for (uint32_t cc = 0; cc < 2; cc++) {
-                if (!walkc[cc].n) continue;
-                // each class on a side stream of its own: a chain of short, latency-bound launches
-                const uint32_t side = cc ? SIDE_JOBS16 : SIDE_JOBS8;
-                HIP_TRY(fork_to(side, q));
-                const uint32_t R3 = walkc_reads[cc], J = (uint32_t)n_jobs[cc];
-                const size_t b_cnt = pad256((size_t)R3 * 4), b_tmp = pad256(scan_temp[cc]), b_job = pad256((size_t)J * 4);
-                char* w2 = part_base + walkc_base[cc];
-                uint32_t* jcnt = (uint32_t*)w2; w2 += b_cnt;
-                uint32_t* joff = (uint32_t*)w2; w2 += b_cnt;
-                void* jtmp = w2; w2 += b_tmp;
-                WalkJobs jb{};
-                jb.n_list = R3;
-                jb.job_off = joff;
-                jb.job_n = job_n;
-                jb.part_score = (int32_t*)w2; w2 += b_job;
-                jb.part_rank = (uint32_t*)w2; w2 += b_job;
-                jb.part_cnt = (uint32_t*)w2;
-                {
-                    bool sorted = false;
-                    int rc = sort_class(PLAN_WALKC8 + cc, 3 + cc, q, sorted);
-                    if (rc != WEPP_OK) return rc;
-                    if (sorted)
-                        for (uint32_t k = 0; k < walkc[cc].n; k++) walkc[cc].p[k].list = val_in + walkc_off[cc];
-                }
-                const uint32_t* list3 = walkc[cc].p[0].list;
-                // gather (list, count in, count out), scan (in, out), combination (list, offset, count, three partial
-                // arrays, four results): what the chain's small kernels move
-                bytes += (uint64_t)R3 * (12 + 8 + 12 + 16) + (uint64_t)J * 12;
-                HIP_TRY(launch_gather_jobs(list3, R3, job_n, jcnt, q));
-                HIP_TRY(launch_exclusive_scan_u32(jcnt, joff, R3, jtmp, scan_temp[cc], q));
-                HIP_TRY(launch_walk_jobs(mat->dev, walkc[cc], PLAN_WALKC8 + cc, info[TI_OPEN + 2 + cc], jb, d_read_off, d_read_word, root_score, mat->d_work, wsid, q));
-                HIP_TRY(launch_finalize_jobs(mat->dev, list3, R3, jb, d_read_off, d_read_word, d_best_bfs_j, d_score,
-                                             d_num_best, d_flags, q));
-                HIP_TRY(join(side));
-            }
+    // (half as much again: the partials of a batch of long reads vary by a third with the tile size its longest
+    // read allows, and a regrowth costs a hipFree + hipMalloc of ~100 MB, 16 ms)
+    WEPP_TRY(c.L->part.reserve(part_need, 2, "partials"));
+    if (!c.scattered && (pl.np || pl.arena_n || pl.seed_n || pl.walkc[0].n || pl.walkc[1].n)) return set_error(WEPP_EDEVICE, "a planned launch without its read list");
+    pl.part_base = (char*)c.L->part.ptr;
+    pl.n_joins = 0;
+    return WEPP_OK;
+}
+
+// the tile plans' lists; the reads that sweep the whole tree go by first listed position (sort_reads.hip); the fork
+int sort_and_fork(const PlaceCall& c, PlanLaunch& pl) {
+    const LaneRegions& r = c.r;
+    for (uint32_t i = 0; i < pl.np; i++) {
+        TilePlan& p = pl.plans[i];
+        p.lst = r.list + p.off;
+        if (c.mat->tun.debug_plans) print_plan_line(stderr, p);
+        if (!p.window && p.t + 1 == c.mat->dev.n_streams && p.count >= SORT_MIN_READS) {
+            HIP_TRY(launch_first_pos(r.list + p.off, p.count, c.rd.off, c.rd.word, r.key_in + p.off, c.f.ps));
+            HIP_TRY(launch_sort_reads(r.key_in + p.off, r.key_out + p.off, r.list + p.off, r.val_in + p.off, p.count, r.sort_tmp, r.sort_temp, c.f.ps));
+            p.lst = r.val_in + p.off;
         }
     }
-    for (uint32_t k = 0; k < n_other; k++) {
-        const Plan& p = plans[others[k]];
+    // Sweeps + finalizes: every chain beside the fused plain sweeps gets a side stream forked from / joined into ps --
+    // behind the sorts -- when the call has more than one chain.  Every plan's finalize follows its sweep.
+    const uint32_t n_walk_chains = (pl.walkc[0].n || pl.walkc[1].n) ? 1u : 0u;
+    const uint32_t n_chains = pl.n_other + n_walk_chains + (pl.arena_n ? 1u : 0u) + (pl.seed_n ? 1u : 0u) + (pl.n_wins ? 1u : 0u);     // launch chains beside the fused plain sweeps
+    pl.fork = (n_chains > 0) && (pl.n_plain > 0 || n_chains > 1);
+    if (pl.fork) HIP_TRY(hipEventRecord(c.L->fork_ev, c.f.ps));
+    return WEPP_OK;
+}
+// A chain beside the fused sweeps runs on side stream i (handle.hpp: SIDE_*) when the call forks, else on ps.
+// The side streams join ps only after everything has been launched: a join in between would make the launches
+// behind it wait for the side stream's kernels.  join(): the chain's last launch is queued; its stream is listed once.
+hipError_t fork_to(const PlaceCall& c, const PlanLaunch& pl, uint32_t i, hipStream_t& q) {
+    q = pl.fork ? c.L->side[i] : c.f.ps;
+    return pl.fork ? hipStreamWaitEvent(q, c.L->fork_ev, 0) : hipSuccess;
+}
+hipError_t join(const PlaceCall& c, PlanLaunch& pl, uint32_t i) {
+    if (!pl.fork) return hipSuccess;
+    const hipError_t e = hipEventRecord(c.L->join_ev[i], c.L->side[i]);
+    if (e == hipSuccess && std::find(pl.joins, pl.joins + pl.n_joins, i) == pl.joins + pl.n_joins) pl.joins[pl.n_joins++] = i;
+    return e;
+}
+
+// A walk class's reads go by (stream, first listed position) when there are enough of them (device_mat.hpp:
+// WALK_SORT_MIN_READS): sorted on the class's own stream, right before its launch.
+// `region` = which of the sort temp regions (1..4; 0 is the whole-tree plan's).  lst: the class's list, sorted or not.
+int sort_class(const PlaceCall& c, uint32_t cls, uint32_t region, hipStream_t q, const uint32_t*& lst) {
+    const LaneRegions& r = c.r;
+    const uint32_t off = c.L->h_info[TI_OFF + plan_id(cls, 0)];
+    const uint32_t cnt = c.L->h_info[TI_OFF + plan_id(cls, 0) + MAX_STREAMS] - off;      // (plan ids of a class are consecutive)
+    lst = r.list + off;
+    if (cnt < WALK_SORT_MIN_READS) return WEPP_OK;
+    HIP_TRY(launch_walk_keys(r.list + off, cnt, c.tier_of, c.rd.off, c.rd.word, r.key_in + off, q));
+    HIP_TRY(launch_sort_reads(r.key_in + off, r.key_out + off, r.list + off, r.val_in + off, cnt, (char*)r.sort_tmp + region * r.sort_temp,
+                              r.sort_temp, q, WALK_SORT_KEY_BITS));
+    lst = r.val_in + off;
+    return WEPP_OK;
+}
+
+// The chunked walks the host plans itself.  The walks write the final per-read results themselves; the plain ones, the
+// chunked ones and the sweeps run side by side (the walks wait on memory most of the time).  Per class: jobs per read
+// in list order -> exclusive scan -> the walk (a partial per job; a job finds its read by bisection in the scanned
+// offsets) -> one combination per read.  Buffers: each class's share of the lane's second block, behind the plans'
+// partials (reserve_partials).
+int launch_chunked_walks(const PlaceCall& c, PlanLaunch& pl) {
+    for (uint32_t cc = 0; cc < 2; cc++) {
+        if (!pl.walkc[cc].n) continue;
+        // each class on a side stream of its own: a chain of short, latency-bound launches
+        const uint32_t side = cc ? SIDE_JOBS16 : SIDE_JOBS8;
         hipStream_t q;
-        HIP_TRY(fork_to(k % OTHER_SIDE_STREAMS, q));
-        int32_t* ps; uint32_t *pr, *pc;
-        parts(p, ps, pr, pc);
-        HIP_TRY(launch_sweep(mat->dev, *p.st, d_read_off, d_read_word, root_score, p.lst, p.count, p.T,
-                             p.ntiles,
-                             p.nchunks, p.bpc, p.s_in_lds, p.dense, p.win_table, p.ent_cap, p.key_cap, p.lds_bytes, ps, pr, pc, q));
-        HIP_TRY(launch_finalize(mat->dev, d_read_off, d_read_word, p.lst, p.count, p.nchunks, ps, pr, pc,
-                                d_best_bfs_j, d_score, d_num_best, d_flags, q));
-        if (k + OTHER_SIDE_STREAMS >= n_other) HIP_TRY(join(k % OTHER_SIDE_STREAMS));     // (the last of these launches on its side stream)
+        HIP_TRY(fork_to(c, pl, side, q));
+        const uint32_t R3 = pl.walkc_reads[cc], J = (uint32_t)pl.n_jobs[cc];
+        const size_t b_cnt = pad256((size_t)R3 * 4), b_tmp = pad256(pl.scan_temp[cc]), b_job = pad256((size_t)J * 4);
+        char* w2 = pl.part_base + pl.walkc_base[cc];
+        uint32_t* jcnt = (uint32_t*)w2; w2 += b_cnt;
+        uint32_t* joff = (uint32_t*)w2; w2 += b_cnt;
+        void* jtmp = w2; w2 += b_tmp;
+        WalkJobs jb{};
+        jb.n_list = R3;
+        jb.job_off = joff;
+        jb.job_n = c.r.job_n;
+        jb.part_score = (int32_t*)w2; w2 += b_job;
+        jb.part_rank = (uint32_t*)w2; w2 += b_job;
+        jb.part_cnt = (uint32_t*)w2;
+        const uint32_t* list3 = nullptr;
+        WEPP_TRY(sort_class(c, PLAN_WALKC8 + cc, 3 + cc, q, list3));
+        WalkPlans wp = pl.walkc[cc];
+        for (uint32_t k = 0; k < wp.n; k++) wp.p[k].list = list3;
+        HIP_TRY(launch_gather_jobs(list3, R3, c.r.job_n, jcnt, q));
+        HIP_TRY(launch_exclusive_scan_u32(jcnt, joff, R3, jtmp, pl.scan_temp[cc], q));
+        HIP_TRY(launch_walk_jobs(c.mat->dev, wp, PLAN_WALKC8 + cc, c.L->h_info[TI_OPEN + 2 + cc], jb, c.rd, c.mat->d_work, q));
+        HIP_TRY(launch_finalize_jobs(c.mat->dev, list3, R3, jb, c.out, q));
+        HIP_TRY(join(c, pl, side));
     }
-    if (n_wins) {
-        // longest chunks first: the workgroups of the largest windows' streams start first
-        std::sort(wins, wins + n_wins, [&](uint32_t a, uint32_t b) { return plans[a].bpc > plans[b].bpc; });
-        WinPlans pl{};
-        uint32_t wg = 0, fin = 0, lds_max = 0;
-        for (uint32_t k = 0; k < n_wins; k++) {
-            const Plan& p = plans[wins[k]];
-            WinPlanDev& d = pl.p[k];
-            d.sid = (uint32_t)(p.st - mat->wstreams.data());
-            d.list = p.lst;
-            d.n_list = p.count; d.T = p.T; d.ntiles = p.ntiles; d.bpc = p.bpc; d.ent_cap = p.ent_cap; d.win_base = p.key_cap; d.nchunks = p.nchunks;
-            parts(p, d.part_score, d.part_rank, d.part_cnt);
-            wg += p.ntiles * (p.nchunks / DENSE_WAVES_PER_WG);
-            d.wg_end = wg;
-            fin += finalize_blocks(p.count, p.nchunks);
-            d.fin_end = fin;
-            lds_max = std::max(lds_max, p.lds_bytes);
-        }
-        pl.n = n_wins;
+    return WEPP_OK;
+}
+
+// the dense and out-of-LDS plans: a launch each, on the side streams in turn
+int launch_own_plans(const PlaceCall& c, PlanLaunch& pl) {
+    for (uint32_t k = 0; k < pl.n_other; k++) {
+        const uint32_t i = pl.others[k];
+        const TilePlan& p = pl.plans[i];
         hipStream_t q;
-        HIP_TRY(fork_to(SIDE_WINDOWS, q));
-        HIP_TRY(launch_sweep_windows(mat->dev, mat->d_wstreams, pl, d_read_off, d_read_word, root_score, lds_max, q));
-        HIP_TRY(launch_finalize_windows(mat->dev, pl, d_read_off, d_read_word, d_best_bfs_j, d_score, d_num_best, d_flags, q));
-        HIP_TRY(join(SIDE_WINDOWS));
+        HIP_TRY(fork_to(c, pl, k % OTHER_SIDE_STREAMS, q));
+        const Partials pt = parts(pl, p.part_off, (size_t)p.nchunks * p.count);
+        HIP_TRY(launch_sweep(c.mat->dev, stream_of(c.mat, p), c.rd, p.lst, p.count, p.T, p.ntiles, p.nchunks, p.bpc, p.s_in_lds, p.dense, p.win_table, p.ent_cap,
+                             p.key_cap, p.lds_bytes, pt.score, pt.rank, pt.cnt, q));
+        HIP_TRY(launch_finalize(c.mat->dev, c.rd, p.lst, p.count, p.nchunks, pt.score, pt.rank, pt.cnt, c.out, q));
+        if (k + OTHER_SIDE_STREAMS >= pl.n_other) HIP_TRY(join(c, pl, k % OTHER_SIDE_STREAMS));     // (the last of these launches on its side stream)
     }
-    if (arena_n) {
-        if (arena_maxk > MAX_TILE_ENTRIES) return set_error(WEPP_ELIMIT, "a read inside one genome window lists more than 8192 positions");
-        const uint32_t cap = (arena_maxk + 63) & ~63u;
-        hipStream_t q;
-        HIP_TRY(fork_to(SIDE_ARENA, q));
-        int32_t* ps = (int32_t*)(part_base + arena_part);
-        uint32_t *pr = (uint32_t*)(ps + (size_t)arena_n * ARENA_CHUNKS), *pc = pr + (size_t)arena_n * ARENA_CHUNKS;
-        HIP_TRY(launch_sweep_arena(mat->dev, mat->dev.wc_streams, wsid, d_read_off, d_read_word, root_score, list + arena_off, arena_n, cap,
-                                   sweep_lds_bytes(mat->dev.bm_words, cap, 0, false), ps, pr, pc, q));
-        HIP_TRY(launch_finalize(mat->dev, d_read_off, d_read_word, list + arena_off, arena_n, ARENA_CHUNKS, ps, pr, pc, d_best_bfs_j, d_score,
-                                d_num_best, d_flags, q));
-        HIP_TRY(join(SIDE_ARENA));
-        passes += arena_n;
+    return WEPP_OK;
+}
+
+// what the records of the two fused launches (SweepPlanDev, WinPlanDev) share; wg_per_tile: sweep workgroups of a tile
+template <typename Dev>
+void fill_fused(Dev& d, const PlanLaunch& pl, const TilePlan& p, uint32_t wg_per_tile, uint32_t& wg, uint32_t& fin, uint32_t& lds_max) {
+    const Partials pt = parts(pl, p.part_off, (size_t)p.nchunks * p.count);
+    d.list = p.lst;
+    d.n_list = p.count; d.T = p.T; d.ntiles = p.ntiles; d.bpc = p.bpc; d.ent_cap = p.ent_cap; d.nchunks = p.nchunks;
+    d.part_score = pt.score; d.part_rank = pt.rank; d.part_cnt = pt.cnt;
+    d.wg_end = wg += p.ntiles * wg_per_tile;
+    d.fin_end = fin += finalize_blocks(p.count, p.nchunks);
+    lds_max = std::max(lds_max, p.lds_bytes);
+}
+
+// the table window plans, fused into one launch
+int launch_window_plans(const PlaceCall& c, PlanLaunch& pl) {
+    if (!pl.n_wins) return WEPP_OK;
+    WinPlans wp{};
+    uint32_t wg = 0, fin = 0, lds_max = 0;
+    for (uint32_t k = 0; k < pl.n_wins; k++) {
+        const TilePlan& p = pl.plans[pl.wins[k]];
+        wp.p[k].sid = p.sid;
+        wp.p[k].win_base = p.key_cap;
+        fill_fused(wp.p[k], pl, p, p.nchunks / DENSE_WAVES_PER_WG, wg, fin, lds_max);
     }
-    if (seed_n) {
-        if (seed_maxk > SEED_MAX_ENTRIES) return set_error(WEPP_EDEVICE, "routing seeded a sample with too many entries");
-        const uint32_t cap = (seed_maxk + 63) & ~63u;
-        hipStream_t q;
-        HIP_TRY(fork_to(SIDE_SEED, q));
-        if (debug_plans) fprintf(stderr, "[plan] seed count=%u maxk=%u chunks=%u lds=%u\n", seed_n, seed_maxk, mat->dev.seed_chunks, seed_lds_bytes(mat->dev, cap));
-        HIP_TRY(launch_seed(mat->dev, mat->streams.back(), list + seed_off, seed_n, cap, d_read_off, d_read_word, root_score, d_best_bfs_j, d_score,
-                            d_num_best, d_flags, mat->d_work, tun.seed_heavy ? L.d_seed_heavy : nullptr, q));
-        HIP_TRY(join(SIDE_SEED));
-        passes += seed_n;
+    wp.n = pl.n_wins;
+    hipStream_t q;
+    HIP_TRY(fork_to(c, pl, SIDE_WINDOWS, q));
+    HIP_TRY(launch_sweep_windows(c.mat->dev, c.mat->d_wstreams, wp, c.rd, lds_max, q));
+    HIP_TRY(launch_finalize_windows(c.mat->dev, wp, c.rd, c.out, q));
+    HIP_TRY(join(c, pl, SIDE_WINDOWS));
+    return WEPP_OK;
+}
+
+// the reads that sweep their window crown (k_sweep_arena)
+int launch_arena(const PlaceCall& c, PlanLaunch& pl) {
+    if (!pl.arena_n) return WEPP_OK;
+    const uint32_t cap = (pl.arena_maxk + 63) & ~63u;
+    const uint32_t* lst = c.r.list + pl.arena_off;
+    hipStream_t q;
+    HIP_TRY(fork_to(c, pl, SIDE_ARENA, q));
+    const Partials pt = parts(pl, pl.arena_part, (size_t)pl.arena_n * ARENA_CHUNKS);
+    HIP_TRY(launch_sweep_arena(c.mat->dev, c.mat->dev.wc_streams, c.rd, lst, pl.arena_n, cap, sweep_lds_bytes(c.mat->dev.bm_words, cap, 0, false), pt.score, pt.rank, pt.cnt, q));
+    HIP_TRY(launch_finalize(c.mat->dev, c.rd, lst, pl.arena_n, ARENA_CHUNKS, pt.score, pt.rank, pt.cnt, c.out, q));
+    HIP_TRY(join(c, pl, SIDE_ARENA));
+    return WEPP_OK;
+}
+
+// the seeded samples (k_seed)
+int launch_seeds(const PlaceCall& c, PlanLaunch& pl) {
+    const wepp_mat_t* mat = c.mat;
+    if (!pl.seed_n) return WEPP_OK;
+    if (pl.seed_maxk > SEED_MAX_ENTRIES) return set_error(WEPP_EDEVICE, "routing seeded a sample with too many entries");
+    const uint32_t cap = (pl.seed_maxk + 63) & ~63u;
+    hipStream_t q;
+    HIP_TRY(fork_to(c, pl, SIDE_SEED, q));
+    if (mat->tun.debug_plans) fprintf(stderr, "[plan] seed count=%u maxk=%u chunks=%u lds=%u\n", pl.seed_n, pl.seed_maxk, mat->dev.seed_chunks, seed_lds_bytes(mat->dev, cap));
+    HIP_TRY(launch_seed(mat->dev, mat->streams.back(), c.r.list + pl.seed_off, pl.seed_n, cap, c.rd, c.out, mat->d_work, mat->tun.seed_heavy ? c.L->d_seed_heavy.ptr : nullptr, q));
+    HIP_TRY(join(c, pl, SIDE_SEED));
+    return WEPP_OK;
+}
+
+// the plain (short-read) plans, fused into one launch on the plan stream
+int launch_plain_plans(const PlaceCall& c, const PlanLaunch& pl) {
+    if (!pl.n_plain) return WEPP_OK;
+    SweepPlans sp{};
+    uint32_t wg = 0, fin = 0, lds_max = 0;
+    for (uint32_t k = 0; k < pl.n_plain; k++) {
+        const TilePlan& p = pl.plans[pl.order[k]];
+        sp.p[k].st = stream_of(c.mat, p);
+        fill_fused(sp.p[k], pl, p, p.nchunks, wg, fin, lds_max);
     }
-    if (n_plain) {
-        SweepPlans pl{};
-        uint32_t wg = 0, fin = 0, lds_max = 0;
-        for (uint32_t k = 0; k < n_plain; k++) {
-            const Plan& p = plans[order[k]];
-            SweepPlanDev& d = pl.p[k];
-            d.st = *p.st;
-            d.list = p.lst;
-            d.n_list = p.count;
-            d.T = p.T;
-            d.ntiles = p.ntiles;
-            d.bpc = p.bpc;
-            d.ent_cap = p.ent_cap;
-            d.nchunks = p.nchunks;
-            parts(p, d.part_score, d.part_rank, d.part_cnt);
-            wg += p.ntiles * p.nchunks;
-            d.wg_end = wg;
-            fin += finalize_blocks(p.count, p.nchunks);
-            d.fin_end = fin;
-            lds_max = std::max(lds_max, p.lds_bytes);
-        }
-        pl.n = n_plain;
-        HIP_TRY(launch_sweep_multi(mat->dev, pl, d_read_off, d_read_word, root_score, lds_max, ps));
-        HIP_TRY(launch_finalize_multi(mat->dev, pl, d_read_off, d_read_word, d_best_bfs_j, d_score, d_num_best, d_flags,
-                                      ps));
-    }
-    for (uint32_t i = 0; i < n_joins; i++) HIP_TRY(hipStreamWaitEvent(ps, L.join_ev[joins[i]], 0));
+    sp.n = pl.n_plain;
+    HIP_TRY(launch_sweep_multi(c.mat->dev, sp, c.rd, lds_max, c.f.ps));
+    HIP_TRY(launch_finalize_multi(c.mat->dev, sp, c.rd, c.out, c.f.ps));
+    return WEPP_OK;
+}
+
+// stage 9.  The side streams' chains join the plan stream, the plan stream and the walks' side streams the caller's;
+// the call's second time stamp and its statistics.
+int join_and_account(const PlaceCall& c, const PlanLaunch& pl, uint32_t plan_total) {
+    wepp_mat_t* mat = c.mat;
+    PlaceLane& L = *c.L;
+    const CallForm& f = c.f;
+    for (uint32_t i = 0; i < pl.n_joins; i++) HIP_TRY(hipStreamWaitEvent(f.ps, L.join_ev[pl.joins[i]], 0));
     bool joined = false;              // something was joined into the caller's stream behind k_step
-    if (walking) {
+    if (f.walking) {
         // the plan stream, when something ran on it behind the counters' copy (k_scatter and what reads its lists: no
         // consumer is launched without it), and the blind walks' side streams join the caller's stream
-        if (scattered) {
-            HIP_TRY(hipEventRecord(L.join_ev[SIDE_PLAN], ps));
-            HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_PLAN], 0));
+        if (c.scattered) {
+            HIP_TRY(hipEventRecord(L.join_ev[SIDE_PLAN], f.ps));
+            HIP_TRY(hipStreamWaitEvent(c.stream, L.join_ev[SIDE_PLAN], 0));
         }
-        if (step_unfused) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_WAVE], 0));
-        if (jobs8_blind || late8) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS8], 0));
-        if (late16[0]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_WALK16], 0));
-        if (late16[1]) HIP_TRY(hipStreamWaitEvent(stream, L.join_ev[SIDE_JOBS16], 0));
-        joined = scattered || step_unfused || jobs8_blind || late8 || late16[0] || late16[1];
+        for (uint32_t i : {SIDE_WAVE, SIDE_JOBS8, SIDE_WALK16, SIDE_JOBS16})
+            if (c.walk_sides >> i & 1u) HIP_TRY(hipStreamWaitEvent(c.stream, L.join_ev[i], 0));
+        joined = c.scattered || c.walk_sides;
     }
     // (the end of the timed span: k_step's own stop event when the kernel is the call's last work on the caller's
     // stream, else a record behind the joins -- which takes the event over from the launch)
-    if (!ev1_on_step || joined) HIP_TRY(hipEventRecord(mat->ev1[ev_slot], stream));
-    {
-        std::lock_guard<std::mutex> lk(mat->stat_mu);
-        mat->last_passes = passes;
-        mat->last_bytes = bytes;
-        mat->acc_passes += passes;
-        mat->acc_bytes += bytes;
-        if (plan_total == n_reads) {            // a call of its own
-            mat->last_n_reads = n_reads;
-            mat->last_walk_reads = walk_reads;
-        } else {                                // a sub-batch (wepp_place_batch reset the sums): complete once every one is in, in any order
-            mat->plan_reads_in += n_reads;
-            mat->last_walk_reads += walk_reads;
-            mat->last_n_reads = mat->plan_reads_in == plan_total ? plan_total : 0;
-        }
+    if (!c.ev1_on_step || joined) HIP_TRY(hipEventRecord(mat->ev1[f.ev_slot], c.stream));
+    std::lock_guard<std::mutex> lk(mat->stat_mu);
+    mat->last_passes = pl.passes;
+    mat->last_bytes = pl.bytes;
+    mat->acc_passes += pl.passes;
+    mat->acc_bytes += pl.bytes;
+    if (plan_total == c.n_reads) {            // a call of its own
+        mat->last_n_reads = c.n_reads;
+        mat->last_walk_reads = pl.walk_reads;
+    } else {                                // a sub-batch (wepp_place_batch reset the sums): complete once every one is in, in any order
+        mat->plan_reads_in += c.n_reads;
+        mat->last_walk_reads += pl.walk_reads;
+        mat->last_n_reads = mat->plan_reads_in == plan_total ? plan_total : 0;
     }
     return WEPP_OK;
+}
+
+}  // namespace
+
+// Two sub-batches of one wepp_place_batch may be inside this function at once, on two host threads and two lanes, and
+// even with one host thread their kernels may overlap on the device (each lane has its own compute stream).  Each lane
+// has its own two device blocks (handle.hpp: the fixed regions, grown before k_route, and the partials, grown once the
+// routing counters are back: a call routes once, whatever its partials need), routing counters, side streams, events
+// and k_seed second-pass table.  What they share on the handle:
+//   - the tree and everything built from it (read-only here);
+//   - the event ring (a slot claimed atomically: choose_form);
+//   - the hints job_events, ww_by_jobs, step_walkers, expect_jobs8 and expect_lists (atomics, read by choose_form and written by store_hints; they choose how the next call cuts its work, never its results);
+//   - the call statistics (stat_mu: join_and_account) and the device counters d_work (device atomics, summed over both lanes);
+//   - d_plan_of / d_wsid_of, of which each sub-batch writes only its own range [plan_base, plan_base + n_reads).
+int place_device(wepp_mat_t* mat, const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t n_reads,
+                 uint32_t* d_best_bfs_j, int32_t* d_score, uint32_t* d_num_best, uint32_t* d_flags, hipStream_t stream,
+                 uint32_t plan_base, uint32_t plan_total, uint32_t lane_idx) {
+    // (a pipelined wepp_place_batch has sized them for the whole call before its sub-batches start, on one thread)
+    WEPP_TRY(ensure_plan_buffers(mat, plan_total));
+    PlaceCall c{mat, &mat->lane[lane_idx], CallReads{d_read_off, d_read_word, nullptr, nullptr}, CallResults{d_best_bfs_j, d_score, d_num_best, d_flags}, n_reads, stream};
+    WEPP_TRY(carve_workspace(c, plan_base));
+    c.f = choose_form(mat, *c.L, n_reads, stream);
+    WEPP_TRY(route_and_launch_blind(c));
+    WEPP_TRY(wait_counters(c));
+    // Who reads `list`: decided HERE, from the counters, for the whole call.
+    const bool need_lists = !c.f.walking || lists_needed(c.L->h_info);
+    store_hints(c, need_lists);
+    WEPP_TRY(launch_late(c, need_lists));
+    PlanLaunch pl;
+    WEPP_TRY(plan_launches(c.L->h_info, mat->tile_reads, c.f.walking, mat->d_wstreams != nullptr, mat->dev, mat->streams.data(), mat->stream_bytes.data(),
+                           mat->wstreams.data(), mat->wstream_bytes.data(), (uint32_t)mat->wstreams.size(), pl));
+    WEPP_TRY(reserve_partials(c, pl));
+    WEPP_TRY(sort_and_fork(c, pl));
+    // (the chains in the order the side streams have always got them)
+    WEPP_TRY(launch_chunked_walks(c, pl));
+    WEPP_TRY(launch_own_plans(c, pl));
+    WEPP_TRY(launch_window_plans(c, pl));
+    WEPP_TRY(launch_arena(c, pl));
+    WEPP_TRY(launch_seeds(c, pl));
+    WEPP_TRY(launch_plain_plans(c, pl));
+    return join_and_account(c, pl, plan_total);
 }
 }  // namespace wepp
 

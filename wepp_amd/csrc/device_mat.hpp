@@ -181,6 +181,11 @@ constexpr uint32_t WALK8_K = 8, WALK8_STACK = 16, WALK16_K = 16, WALK16_STACK = 
 constexpr uint32_t WALK_DELTA_BITS = 7, WALK_DELTA_BIAS = 64;
 static_assert(2 * WALK16_K < WALK_DELTA_BIAS, "a node's delta must fit the stack entry's delta field");
 constexpr uint32_t WALK8_ROWS = WALK8_STACK, WALK16_ROWS = WALK16_STACK;   // (default stack rows: see WALK_WAVES above)
+// The two records every placement launcher takes (the launcher unpacks them into its kernel's parameter list).
+// CallReads: the reads of a call -- read r owns word[off[r] .. off[r + 1]) --, their root scores and the arena slice
+// each walks (k_route writes both).  CallResults: the four result arrays of the call, one element per read.
+struct CallReads { const uint32_t *off, *word; const int32_t* root_score; const uint32_t* wsid; };
+struct CallResults { uint32_t* best_bfs_j; int32_t* score; uint32_t *num_best, *flags; };
 struct WalkPlanDev {
     uint32_t tier, n_list, wave_end, job0;   // wave_end = first wave (of the launch) after this plan;
     const uint32_t* list;                    // chunked: n_list jobs numbered from job0, list = the class's whole list
@@ -203,22 +208,16 @@ struct WalkPlans {
 // the plain walks of one class (cls = 0 / 1, a wave = 64 reads; writes the final per-read results) sized BLIND: the reads are list[0 .. *count) (k_route's list and cursor, both on the device),
 // the grid is the worst case (max_reads lanes), every read walks the arena slice wsid names; waves beyond the count leave
 hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, uint32_t max_reads, const uint32_t* list, const uint32_t* count,
-                             const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                             int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid,
-                             hipStream_t stream);
+                             const CallReads& rd, const CallResults& out, unsigned long long* work_counter, hipStream_t stream);
 // the chunked walks of one call: job counts gathered into list order (scan input), the walk itself (partials per job) and the combination per read
 hipError_t launch_gather_jobs(const uint32_t* list, uint32_t n_list, const uint32_t* job_n, uint32_t* out, hipStream_t stream);
-hipError_t launch_walk_jobs(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const WalkJobs& jb, const uint32_t* d_read_off,
-                            const uint32_t* d_read_word, const int32_t* root_score, unsigned long long* work_counter,
-                            const uint32_t* wsid, hipStream_t stream);
-hipError_t launch_finalize_jobs(const DevMAT& m, const uint32_t* list, uint32_t n_list, const WalkJobs& jb,
-                                const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t* best_bfs_j,
-                                int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream);
+hipError_t launch_walk_jobs(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const WalkJobs& jb, const CallReads& rd,
+                            unsigned long long* work_counter, hipStream_t stream);
+hipError_t launch_finalize_jobs(const DevMAT& m, const uint32_t* list, uint32_t n_list, const WalkJobs& jb, const CallResults& out, hipStream_t stream);
 // the reads with many events: list[0 .. count[0]) a wave each, list[n_reads - count[1] .. n_reads) a block each (k_route's
 // two-ended list and its cursors), a persistent grid
-hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_t* count, uint32_t n_reads, const uint32_t* d_read_off,
-                            const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
-                            uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
+hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_t* count, uint32_t n_reads, const CallReads& rd, const CallResults& out,
+                            unsigned long long* work_counter, hipStream_t stream);
 // wave-role workgroups of k_step (WALK_WAVES waves each) at the most: beyond, they loop over the reads with many events.
 // A million reads of a sequencing run hold ~300 reads with more than 64 events (a workgroup each) and ~3 700 smaller ones
 // (a wave each): ~2 150 workgroups.  With 1 024 the workgroups of the large reads took small ones behind them, on the
@@ -242,15 +241,13 @@ constexpr uint32_t STEP_GROUPS_MAX_WALKERS = 75000;
 // stop: as launch_route's.
 struct StepReport { const uint32_t* tier_info; uint32_t* report; uint32_t seq; };
 hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
-                       const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream,
+                       const uint32_t* wwcount, const CallReads& rd, const CallResults& out, unsigned long long* work_counter, hipStream_t stream,
                        const StepReport& rep = StepReport{nullptr, nullptr, 0u}, hipEvent_t stop = nullptr);
 // a chunked class sized blind: jobs[0 .. *n_jobs) (k_route's table), partials into jb.part_*, then the combination over
 // clist[0 .. *n_class); both leave at once when *jb.skip != 0
 hipError_t launch_walk_jobs_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, const WalkJobs& jb, const uint32_t* jobs, const uint32_t* n_jobs,
-                                  const uint32_t* clist, const uint32_t* n_class, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                                  const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags,
-                                  unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream);
+                                  const uint32_t* clist, const uint32_t* n_class, const CallReads& rd, const CallResults& out,
+                                  unsigned long long* work_counter, hipStream_t stream);
 hipError_t scan_u32_temp_bytes(uint32_t n, size_t* bytes);
 hipError_t launch_exclusive_scan_u32(const uint32_t* in, uint32_t* out, uint32_t n, void* temp, size_t temp_bytes,
                                      hipStream_t stream);
@@ -333,10 +330,8 @@ hipError_t launch_rebase_index(IxHead* heads, uint32_t n_heads, IxEnt* ents, uin
 uint32_t seed_lds_bytes(const DevMAT& m, uint32_t ent_cap);
 hipError_t seed_set_max_lds(uint32_t bytes);
 size_t seed_heavy_bytes();      // the second pass's table (handle.hpp: d_seed_heavy)
-hipError_t launch_seed(const DevMAT& m, const DevStream& full, const uint32_t* list, uint32_t n_list, uint32_t ent_cap,
-                       const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score,
-                       uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags,
-                       unsigned long long* work_counter, void* heavy_table, hipStream_t stream);
+hipError_t launch_seed(const DevMAT& m, const DevStream& full, const uint32_t* list, uint32_t n_list, uint32_t ent_cap, const CallReads& rd,
+                       const CallResults& out, unsigned long long* work_counter, void* heavy_table, hipStream_t stream);
 // order of the reads that sweep the whole-tree stream: by first listed position (sort_reads.hip)
 constexpr uint32_t SORT_KEY_BITS = 21;      // position + 1 (0 = the read lists nothing)
 constexpr uint32_t SORT_MIN_READS = 4096;   // below this a sweep costs less than the sort
@@ -356,10 +351,7 @@ hipError_t launch_sort_reads(const uint32_t* keys_in, uint32_t* keys_out, const 
 // scatter: read indices grouped by tier into `list` (tier t occupies [tier_off[t], tier_off[t+1]))
 hipError_t launch_scatter(const uint8_t* tier_of, const uint32_t* slot_in_blk, uint32_t n_reads, const uint32_t* blk_counts,
                           uint32_t* tier_info, uint32_t* list, bool skip_plain_walks, hipStream_t stream);
-hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const uint32_t* d_read_off,
-                        const uint32_t* d_read_word, const int32_t* root_score, const uint32_t* list,
-                        uint32_t n_list, uint32_t T,
-                        uint32_t ntiles, uint32_t nchunks, uint32_t blocks_per_chunk, bool s_in_lds, bool dense,
+hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const CallReads& rd, const uint32_t* list, uint32_t n_list, uint32_t T, uint32_t ntiles, uint32_t nchunks, uint32_t blocks_per_chunk, bool s_in_lds, bool dense,
                         bool win_table, uint32_t ent_cap, uint32_t key_cap, uint32_t lds_bytes, int32_t* part_score,
                         uint32_t* part_rank, uint32_t* part_cnt, hipStream_t stream);
 // waves of a dense / window workgroup (one tile: they share its tables and sweep a chunk each).  16: a window's
@@ -402,18 +394,13 @@ constexpr uint32_t MAX_TILE_ENTRIES = 8192;
 constexpr uint32_t DENSE_MAX_POS = (1u << 19) - 1;
 constexpr uint32_t DENSE_MIN_READ_WORDS = 16; // tiles of reads this long keep the sorted position index
 constexpr uint32_t ARENA_CHUNKS = 16;      // waves (chunks of its window crown) per read of k_sweep_arena
-hipError_t launch_sweep_arena(const DevMAT& m, const DevStream* wc_streams, const uint32_t* wsid, const uint32_t* d_read_off,
-                              const uint32_t* d_read_word, const int32_t* root_score, const uint32_t* list, uint32_t n_list,
+hipError_t launch_sweep_arena(const DevMAT& m, const DevStream* wc_streams, const CallReads& rd, const uint32_t* list, uint32_t n_list,
                               uint32_t ent_cap, uint32_t lds_bytes, int32_t* part_score, uint32_t* part_rank, uint32_t* part_cnt,
                               hipStream_t stream);
 // every window plan of a call in one launch, and their combination in one
-hipError_t launch_sweep_windows(const DevMAT& m, const DevStream* d_wstreams, const WinPlans& pl, const uint32_t* d_read_off,
-                                const uint32_t* d_read_word, const int32_t* root_score, uint32_t lds_bytes, hipStream_t stream);
-hipError_t launch_finalize_windows(const DevMAT& m, const WinPlans& pl, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                                   uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream);
-hipError_t launch_sweep_multi(const DevMAT& m, const SweepPlans& pl, const uint32_t* d_read_off,
-                              const uint32_t* d_read_word, const int32_t* root_score, uint32_t lds_bytes,
-                              hipStream_t stream);
+hipError_t launch_sweep_windows(const DevMAT& m, const DevStream* d_wstreams, const WinPlans& pl, const CallReads& rd, uint32_t lds_bytes, hipStream_t stream);
+hipError_t launch_finalize_windows(const DevMAT& m, const WinPlans& pl, const CallReads& rd, const CallResults& out, hipStream_t stream);
+hipError_t launch_sweep_multi(const DevMAT& m, const SweepPlans& pl, const CallReads& rd, uint32_t lds_bytes, hipStream_t stream);
 // finalize: 1, 4, 16 or 64 lanes per read by the number of chunk partials it has to combine (a wave holds
 // 64 / lanes consecutive reads: partial loads stay coalesced); 256-thread blocks.  One wave per read for
 // every plan beyond 8 chunks (the previous rule) made 60 % of the threads of a default step
@@ -424,13 +411,9 @@ inline uint32_t finalize_blocks(uint32_t n_list, uint32_t nchunks) {
     const uint32_t reads_per_block = 256 / finalize_lanes_per_read(nchunks);
     return (n_list + reads_per_block - 1) / reads_per_block;
 }
-hipError_t launch_finalize_multi(const DevMAT& m, const SweepPlans& pl, const uint32_t* d_read_off,
-                                 const uint32_t* d_read_word, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
-                                 uint32_t* flags, hipStream_t stream);
-hipError_t launch_finalize(const DevMAT& m, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                           const uint32_t* list, uint32_t n_list, uint32_t nchunks, const int32_t* part_score,
-                           const uint32_t* part_rank, const uint32_t* part_cnt, uint32_t* best_bfs_j,
-                           int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream);
+hipError_t launch_finalize_multi(const DevMAT& m, const SweepPlans& pl, const CallReads& rd, const CallResults& out, hipStream_t stream);
+hipError_t launch_finalize(const DevMAT& m, const CallReads& rd, const uint32_t* list, uint32_t n_list, uint32_t nchunks, const int32_t* part_score,
+                           const uint32_t* part_rank, const uint32_t* part_cnt, const CallResults& out, hipStream_t stream);
 // k_scores runs one wave per (read, chunk of the stream).  The chunks of a launch: enough waves to fill the chip
 // (PASS2_TARGET_WAVES over the reads), cut at checkpoints; the list of optimal nodes (emit) takes no chunk shorter than
 // PASS2_MIN_CHUNK_BLOCKS blocks.  launch_scores and launch_best_nodes both launch what this returns, and the

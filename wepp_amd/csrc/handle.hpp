@@ -140,12 +140,12 @@ struct DevBlock { void* ptr; size_t bytes, asked; };
 // of sub-batch k+1 (kernels, a device-to-host copy, the host's poll) overlaps the walks of sub-batch k, each lane's
 // work ordered on the lane's own compute stream.  wepp_place_batch_device uses lane 0.
 struct PlaceLane {
-    // Two grow-only blocks, sized at the two moments a call knows the sizes (capi.cpp: place_device).
+    // Two grow-only blocks, sized at the two moments a call knows the sizes (capi.cpp: carve_workspace, reserve_partials).
     // ws: the regions sized by the number of reads alone -- read list, root scores, routing arrays, walk lists, blind job
     // tables, sort keys and scratch.  Grown before k_route, which writes into it: it does not move during a call.
     GrowBuf<> ws;
     // part: what is sized from the routing counters -- 12 bytes per (chunk, read) of every sweep plan and, behind them,
-    // the job tables and partials of the chunked walks the host plans itself.  Grown behind the plan loop, before
+    // the job tables and partials of the chunked walks the host plans itself.  Grown behind the planner (capi.cpp: reserve_partials), before
     // anything of the call has touched it.
     GrowBuf<> part;
     DevMem<uint32_t> d_info;          // two sets of tier_info (TI_WORDS each, used alternately: k_route clears the other one) followed by blk_counts
@@ -168,12 +168,13 @@ struct PlaceLane {
     DevMem<> d_seed_heavy;
 };
 
-// Which of a lane's side streams (and join events, same index) a launch chain of place_device runs on.  The values are
+// Which of a lane's side streams (and join events, same index) a launch chain of place_device runs on (capi.cpp: the
+// stages route_and_launch_blind, launch_late_classes and the launch_* chains behind the planner).  The values are
 // the ones every measurement was taken with and must not change.  The plans launched on their own (dense, out-of-LDS,
 // window plans beyond MAX_WINDOWS) take side[k % OTHER_SIDE_STREAMS] in turn, so some streams serve twice: stream 10 is
 // the 16-entry plain walk class AND the fused window plans, stream 9 is the plan stream AND the tenth such plan (11 and
 // 12, seeds and arena, the twelfth and thirteenth).  Chains that share a stream run one behind the other, no more.
-constexpr uint32_t SIDE_WAVE = MAX_STREAMS - 1;        // k_walk_wave of WEPP_STEP_UNFUSED=1
+constexpr uint32_t SIDE_WAVE = MAX_STREAMS - 1;        // k_walk_wave of WEPP_STEP_UNFUSED=1 (route_and_launch_blind)
 constexpr uint32_t SIDE_JOBS8 = MAX_STREAMS - 2;       // the 8-entry job class, blind or planned
 constexpr uint32_t SIDE_JOBS16 = MAX_STREAMS - 3;      // the 16-entry job class
 constexpr uint32_t SIDE_WALK16 = MAX_STREAMS - 6;      // the plain walks of 9 - 16 entries

@@ -473,19 +473,17 @@ uint32_t seed_lds_bytes(const DevMAT& m, uint32_t ent_cap) {
     return (m.bm_words + ent_cap + (SEED_MAX_HARD + 1) + seed_h_words(m.seed_chunks) + SEED_SHARED_WORDS + SEED_WAVES * 3 * SEED_HIT_CAP) * 4;
 }
 
-hipError_t launch_seed(const DevMAT& m, const DevStream& full, const uint32_t* list, uint32_t n_list, uint32_t ent_cap,
-                       const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score,
-                       uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags,
-                       unsigned long long* work_counter, void* heavy_table, hipStream_t stream) {
+hipError_t launch_seed(const DevMAT& m, const DevStream& full, const uint32_t* list, uint32_t n_list, uint32_t ent_cap, const CallReads& rd,
+                       const CallResults& out, unsigned long long* work_counter, void* heavy_table, hipStream_t stream) {
     if (n_list == 0) return hipSuccess;
     SeedHeavy* heavy = static_cast<SeedHeavy*>(heavy_table);       // (zeroed at creation, cleared by the finalize kernel; nullptr: one pass)
     hipLaunchKernelGGL(k_seed<false>, dim3(n_list), dim3(SEED_THREADS), seed_lds_bytes(m, ent_cap), stream, m, full, list, n_list, ent_cap,
-                       d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, heavy);
+                       rd.off, rd.word, rd.root_score, out.best_bfs_j, out.score, out.num_best, out.flags, work_counter, heavy);
     if (heavy) {
         // sized for the whole table: the number of deferred samples stays on the device (workgroups beyond it leave at once)
         hipLaunchKernelGGL(k_seed<true>, dim3(SEED_HEAVY_CAP * SEED_HEAVY_PARTS), dim3(SEED_THREADS), seed_lds_bytes(m, ent_cap), stream, m, full,
-                           list, n_list, ent_cap, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, heavy);
-        hipLaunchKernelGGL(k_seed_heavy_finalize, dim3(1), dim3(256), 0, stream, m, heavy, d_read_off, d_read_word, best_bfs_j, score, num_best, flags);
+                           list, n_list, ent_cap, rd.off, rd.word, rd.root_score, out.best_bfs_j, out.score, out.num_best, out.flags, work_counter, heavy);
+        hipLaunchKernelGGL(k_seed_heavy_finalize, dim3(1), dim3(256), 0, stream, m, heavy, rd.off, rd.word, out.best_bfs_j, out.score, out.num_best, out.flags);
     }
     return hipGetLastError();
 }

@@ -1042,10 +1042,7 @@ __global__ void k_finalize_windows(DevMAT m, WinPlans pl, const uint32_t* __rest
 // -----------------------------------------------------------------------------
 // launchers (called from capi.cpp)
 // -----------------------------------------------------------------------------
-hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const uint32_t* d_read_off,
-                        const uint32_t* d_read_word, const int32_t* root_score, const uint32_t* list,
-                        uint32_t n_list, uint32_t T,
-                        uint32_t ntiles, uint32_t nchunks, uint32_t blocks_per_chunk, bool s_in_lds, bool dense,
+hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const CallReads& rd, const uint32_t* list, uint32_t n_list, uint32_t T, uint32_t ntiles, uint32_t nchunks, uint32_t blocks_per_chunk, bool s_in_lds, bool dense,
                         bool win_table, uint32_t ent_cap, uint32_t key_cap, uint32_t lds_bytes, int32_t* part_score,
                         uint32_t* part_rank, uint32_t* part_cnt, hipStream_t stream) {
     // nchunks is a multiple of DENSE_WAVES_PER_WG for the dense variant (capi.cpp)
@@ -1053,7 +1050,7 @@ hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const uint32_t* d_
     const dim3 block(dense ? 64 * DENSE_WAVES_PER_WG : 64);
 #define WEPP_SWEEP(A, B, C, CAP, KCAP)                                                                                \
     hipLaunchKernelGGL((k_sweep<A, B, C>), grid, block, lds_bytes, stream, st, m.bm_words, m.max_pos, CAP, KCAP,       \
-                       d_read_off, d_read_word, root_score, list, n_list, T, ntiles, blocks_per_chunk, part_score,    \
+                       rd.off, rd.word, rd.root_score, list, n_list, T, ntiles, blocks_per_chunk, part_score,    \
                        part_rank, part_cnt)
     // (win_table: key_cap carries the window's first position)
     if (s_in_lds && dense && win_table) WEPP_SWEEP(true, true, true, ent_cap, key_cap);
@@ -1064,61 +1061,52 @@ hipError_t launch_sweep(const DevMAT& m, const DevStream& st, const uint32_t* d_
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_arena(const DevMAT& m, const DevStream* wc_streams, const uint32_t* wsid, const uint32_t* d_read_off,
-                              const uint32_t* d_read_word, const int32_t* root_score, const uint32_t* list, uint32_t n_list,
+hipError_t launch_sweep_arena(const DevMAT& m, const DevStream* wc_streams, const CallReads& rd, const uint32_t* list, uint32_t n_list,
                               uint32_t ent_cap, uint32_t lds_bytes, int32_t* part_score, uint32_t* part_rank, uint32_t* part_cnt,
                               hipStream_t stream) {
     if (n_list == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_sweep_arena, dim3(n_list * ARENA_CHUNKS), dim3(64), lds_bytes, stream, wc_streams, wsid, m.bm_words, m.max_pos, ent_cap,
-                       d_read_off, d_read_word, root_score, list, n_list, part_score, part_rank, part_cnt);
+    hipLaunchKernelGGL(k_sweep_arena, dim3(n_list * ARENA_CHUNKS), dim3(64), lds_bytes, stream, wc_streams, rd.wsid, m.bm_words, m.max_pos, ent_cap,
+                       rd.off, rd.word, rd.root_score, list, n_list, part_score, part_rank, part_cnt);
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_multi(const DevMAT& m, const SweepPlans& pl, const uint32_t* d_read_off,
-                              const uint32_t* d_read_word, const int32_t* root_score, uint32_t lds_bytes,
-                              hipStream_t stream) {
+hipError_t launch_sweep_multi(const DevMAT& m, const SweepPlans& pl, const CallReads& rd, uint32_t lds_bytes, hipStream_t stream) {
     if (pl.n == 0) return hipSuccess;
     // lds_bytes = the largest request of one sweep; every wave of a workgroup gets that much
     const uint32_t units = pl.p[pl.n - 1].wg_end;
     hipLaunchKernelGGL(k_sweep_multi, dim3((units + SWEEP_WAVES - 1) / SWEEP_WAVES), dim3(64 * SWEEP_WAVES),
-                       lds_bytes * SWEEP_WAVES, stream, pl, m.bm_words, m.max_pos, lds_bytes / 4, d_read_off, d_read_word,
-                       root_score);
+                       lds_bytes * SWEEP_WAVES, stream, pl, m.bm_words, m.max_pos, lds_bytes / 4, rd.off, rd.word,
+                       rd.root_score);
     return hipGetLastError();
 }
 
-hipError_t launch_sweep_windows(const DevMAT& m, const DevStream* d_wstreams, const WinPlans& pl, const uint32_t* d_read_off,
-                                const uint32_t* d_read_word, const int32_t* root_score, uint32_t lds_bytes, hipStream_t stream) {
+hipError_t launch_sweep_windows(const DevMAT& m, const DevStream* d_wstreams, const WinPlans& pl, const CallReads& rd, uint32_t lds_bytes, hipStream_t stream) {
     if (pl.n == 0) return hipSuccess;
     hipLaunchKernelGGL(k_sweep_windows, dim3(pl.p[pl.n - 1].wg_end), dim3(64 * DENSE_WAVES), lds_bytes, stream, d_wstreams, pl, m.bm_words,
-                       m.max_pos, d_read_off, d_read_word, root_score);
+                       m.max_pos, rd.off, rd.word, rd.root_score);
     return hipGetLastError();
 }
 
-hipError_t launch_finalize_windows(const DevMAT& m, const WinPlans& pl, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                                   uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream) {
+hipError_t launch_finalize_windows(const DevMAT& m, const WinPlans& pl, const CallReads& rd, const CallResults& out, hipStream_t stream) {
     if (pl.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_finalize_windows, dim3(pl.p[pl.n - 1].fin_end), dim3(256), 0, stream, m, pl, d_read_off, d_read_word, best_bfs_j,
-                       score, num_best, flags);
+    hipLaunchKernelGGL(k_finalize_windows, dim3(pl.p[pl.n - 1].fin_end), dim3(256), 0, stream, m, pl, rd.off, rd.word, out.best_bfs_j,
+                       out.score, out.num_best, out.flags);
     return hipGetLastError();
 }
 
-hipError_t launch_finalize_multi(const DevMAT& m, const SweepPlans& pl, const uint32_t* d_read_off,
-                                 const uint32_t* d_read_word, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
-                                 uint32_t* flags, hipStream_t stream) {
+hipError_t launch_finalize_multi(const DevMAT& m, const SweepPlans& pl, const CallReads& rd, const CallResults& out, hipStream_t stream) {
     if (pl.n == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_finalize_multi, dim3(pl.p[pl.n - 1].fin_end), dim3(256), 0, stream, m, pl, d_read_off,
-                       d_read_word, best_bfs_j, score, num_best, flags);
+    hipLaunchKernelGGL(k_finalize_multi, dim3(pl.p[pl.n - 1].fin_end), dim3(256), 0, stream, m, pl, rd.off, rd.word, out.best_bfs_j,
+                       out.score, out.num_best, out.flags);
     return hipGetLastError();
 }
 
-hipError_t launch_finalize(const DevMAT& m, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                           const uint32_t* list, uint32_t n_list, uint32_t nchunks, const int32_t* part_score,
-                           const uint32_t* part_rank, const uint32_t* part_cnt, uint32_t* best_bfs_j,
-                           int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream) {
+hipError_t launch_finalize(const DevMAT& m, const CallReads& rd, const uint32_t* list, uint32_t n_list, uint32_t nchunks, const int32_t* part_score,
+                           const uint32_t* part_rank, const uint32_t* part_cnt, const CallResults& out, hipStream_t stream) {
     const uint32_t lpr = finalize_lanes_per_read(nchunks);
     const dim3 grid(finalize_blocks(n_list, nchunks)), block(256);
-#define FIN(L) hipLaunchKernelGGL(k_finalize<L>, grid, block, 0, stream, m, d_read_off, d_read_word, list, n_list, nchunks, \
-                                  part_score, part_rank, part_cnt, best_bfs_j, score, num_best, flags)
+#define FIN(L) hipLaunchKernelGGL(k_finalize<L>, grid, block, 0, stream, m, rd.off, rd.word, list, n_list, nchunks, \
+                                  part_score, part_rank, part_cnt, out.best_bfs_j, out.score, out.num_best, out.flags)
     if (lpr == 1) FIN(1);
     else if (lpr == 4) FIN(4);
     else if (lpr == 16) FIN(16);

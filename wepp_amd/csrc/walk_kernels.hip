@@ -734,31 +734,31 @@ static uint32_t walk_lds_bytes(uint32_t kw, uint32_t sd_rows) { return WALK_WAVE
 // scratch, never more than the class admits
 static uint32_t walk_stack_rows(uint32_t open_max, uint32_t sd) { return std::min(sd, std::max(open_max, 2u)); }
 
-hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, uint32_t max_reads, const uint32_t* list, const uint32_t* count,
-                             const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                             int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid,
-                             hipStream_t stream) {
-    if (max_reads == 0) return hipSuccess;
-    const uint32_t waves = walk_plan_waves(max_reads);
-    const dim3 grid(waves / WALK_WAVES), block(64 * WALK_WAVES);
-    WalkPlans pl{};
-    pl.n = 1;
-    const WalkJobs none{};
-    if (cls == PLAN_WALK8) {
-        const uint32_t sd = walk_stack_rows(stack_rows, WALK8_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK8_K, (int)WALK8_STACK, false>), grid, block, walk_lds_bytes(WALK8_K, sd), stream, m, pl,
-                           none, sd, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, list, count);
-    } else {
-        const uint32_t sd = walk_stack_rows(stack_rows, WALK16_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK16_K, (int)WALK16_STACK, false>), grid, block, walk_lds_bytes(WALK16_K, sd), stream, m, pl,
-                           none, sd, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, list, count);
-    }
+// k_walk of one class (WALK8 / WALK16 by cls8) over pl, JOBS = the chunked form (partials into jb, no results): one
+// launch for the three launchers below
+template <bool JOBS>
+static hipError_t launch_k_walk(bool cls8, uint32_t waves, const DevMAT& m, const WalkPlans& pl, const WalkJobs& jb, uint32_t rows, const CallReads& rd, const CallResults& out,
+                                unsigned long long* work_counter, const uint32_t* list, const uint32_t* count, hipStream_t stream) {
+    const dim3 grid((waves + WALK_WAVES - 1) / WALK_WAVES), block(64 * WALK_WAVES);
+    const uint32_t sd = walk_stack_rows(rows, cls8 ? WALK8_STACK : WALK16_STACK);
+#define WEPP_WALK(K, S) hipLaunchKernelGGL((k_walk<(int)K, (int)S, JOBS>), grid, block, walk_lds_bytes(K, sd), stream, m, pl, jb, sd, rd.off, rd.word, rd.root_score, \
+                                           out.best_bfs_j, out.score, out.num_best, out.flags, work_counter, rd.wsid, list, count)
+    if (cls8) WEPP_WALK(WALK8_K, WALK8_STACK);
+    else WEPP_WALK(WALK16_K, WALK16_STACK);
+#undef WEPP_WALK
     return hipGetLastError();
 }
 
+hipError_t launch_walk_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, uint32_t max_reads, const uint32_t* list, const uint32_t* count,
+                             const CallReads& rd, const CallResults& out, unsigned long long* work_counter, hipStream_t stream) {
+    if (max_reads == 0) return hipSuccess;
+    WalkPlans pl{};
+    pl.n = 1;
+    return launch_k_walk<false>(cls == PLAN_WALK8, walk_plan_waves(max_reads), m, pl, WalkJobs{}, stack_rows, rd, out, work_counter, list, count, stream);
+}
+
 hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uint32_t max_reads, const uint32_t* wlist, const uint32_t* wcount, const uint32_t* wwlist,
-                       const uint32_t* wwcount, const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j,
-                       int32_t* score, uint32_t* num_best, uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream,
+                       const uint32_t* wwcount, const CallReads& rd, const CallResults& out, unsigned long long* work_counter, hipStream_t stream,
                        const StepReport& rep, hipEvent_t stop) {
     static_assert(STEP_WAVE_WGS % WALK_XCDS == 0 && WALK_PLAN_ALIGN % (WALK_XCDS * WALK_WAVES) == 0,
                   "the workgroups behind the wave-role ones keep their XCD order, and their number is a multiple of the XCDs");
@@ -769,7 +769,7 @@ hipError_t launch_step(const DevMAT& m, uint32_t group, uint32_t stack_rows, uin
     // (the grid is the one of lane = read whatever the form: with groups its workgroups loop when the list needs more)
     const dim3 grid(wave_cap + walk_plan_waves(max_reads) / WALK_WAVES), block(64 * WALK_WAVES);
     if (rep.report && !rep.tier_info) return hipErrorInvalidValue;
-#define WEPP_STEP_ARGS m, sd, wave_cap, max_reads, d_read_off, d_read_word, root_score, best_bfs_j, score, num_best, flags, work_counter, wsid, wlist, wcount, wwlist, wwcount, \
+#define WEPP_STEP_ARGS m, sd, wave_cap, max_reads, rd.off, rd.word, rd.root_score, out.best_bfs_j, out.score, out.num_best, out.flags, work_counter, rd.wsid, wlist, wcount, wwlist, wwcount, \
                        rep.tier_info, rep.report, rep.seq
     // (a stop event rides on the kernel's own dispatch packet, as in launch_route)
 #define WEPP_STEP_LAUNCH(G, lds)                                                                                  \
@@ -795,58 +795,28 @@ hipError_t launch_gather_jobs(const uint32_t* list, uint32_t n_list, const uint3
     return hipGetLastError();
 }
 
-hipError_t launch_walk_jobs(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const WalkJobs& jb,
-                            const uint32_t* d_read_off, const uint32_t* d_read_word, const int32_t* root_score,
-                            unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
+hipError_t launch_walk_jobs(const DevMAT& m, const WalkPlans& pl, uint32_t cls, uint32_t open_max, const WalkJobs& jb, const CallReads& rd,
+                            unsigned long long* work_counter, hipStream_t stream) {
     if (pl.n == 0) return hipSuccess;
-    const uint32_t waves = pl.p[pl.n - 1].wave_end;
-    const dim3 grid((waves + WALK_WAVES - 1) / WALK_WAVES), block(64 * WALK_WAVES);
-    if (cls == PLAN_WALKC8) {
-        const uint32_t sd = walk_stack_rows(open_max, WALK8_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK8_K, (int)WALK8_STACK, true>), grid, block, walk_lds_bytes(WALK8_K, sd), stream, m, pl, jb,
-                           sd, d_read_off, d_read_word, root_score, (uint32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, work_counter, wsid, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    } else {
-        const uint32_t sd = walk_stack_rows(open_max, WALK16_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK16_K, (int)WALK16_STACK, true>), grid, block, walk_lds_bytes(WALK16_K, sd), stream, m, pl, jb,
-                           sd, d_read_off, d_read_word, root_score, (uint32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, work_counter, wsid, (const uint32_t*)nullptr, (const uint32_t*)nullptr);
-    }
-    return hipGetLastError();
+    return launch_k_walk<true>(cls == PLAN_WALKC8, pl.p[pl.n - 1].wave_end, m, pl, jb, open_max, rd, CallResults{}, work_counter, nullptr, nullptr, stream);
 }
 
-hipError_t launch_finalize_jobs(const DevMAT& m, const uint32_t* list, uint32_t n_list, const WalkJobs& jb,
-                                const uint32_t* d_read_off, const uint32_t* d_read_word, uint32_t* best_bfs_j,
-                                int32_t* score, uint32_t* num_best, uint32_t* flags, hipStream_t stream) {
+hipError_t launch_finalize_jobs(const DevMAT& m, const uint32_t* list, uint32_t n_list, const WalkJobs& jb, const CallResults& out, hipStream_t stream) {
     if (n_list == 0) return hipSuccess;
     hipLaunchKernelGGL(k_finalize_jobs, dim3((n_list + 255) / 256), dim3(256), 0, stream, m, list, n_list, jb,
-                       best_bfs_j, score, num_best, flags, (const uint32_t*)nullptr);
+                       out.best_bfs_j, out.score, out.num_best, out.flags, (const uint32_t*)nullptr);
     return hipGetLastError();
 }
 
 hipError_t launch_walk_jobs_blind(const DevMAT& m, uint32_t cls, uint32_t stack_rows, const WalkJobs& jb, const uint32_t* jobs, const uint32_t* n_jobs,
-                                  const uint32_t* clist, const uint32_t* n_class, const uint32_t* d_read_off, const uint32_t* d_read_word,
-                                  const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best, uint32_t* flags,
-                                  unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
-    const uint32_t waves = walk_plan_waves(BLIND_JOB_CAP);
-    const dim3 grid(waves / WALK_WAVES), block(64 * WALK_WAVES);
+                                  const uint32_t* clist, const uint32_t* n_class, const CallReads& rd, const CallResults& out,
+                                  unsigned long long* work_counter, hipStream_t stream) {
     WalkPlans pl{};
     pl.n = 1;
-    if (cls == PLAN_WALKC8) {
-        const uint32_t sd = walk_stack_rows(stack_rows, WALK8_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK8_K, (int)WALK8_STACK, true>), grid, block, walk_lds_bytes(WALK8_K, sd), stream, m, pl, jb,
-                           sd, d_read_off, d_read_word, root_score, (uint32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, work_counter, wsid, jobs, n_jobs);
-    } else {
-        const uint32_t sd = walk_stack_rows(stack_rows, WALK16_STACK);
-        hipLaunchKernelGGL((k_walk<(int)WALK16_K, (int)WALK16_STACK, true>), grid, block, walk_lds_bytes(WALK16_K, sd), stream, m, pl, jb,
-                           sd, d_read_off, d_read_word, root_score, (uint32_t*)nullptr, (int32_t*)nullptr, (uint32_t*)nullptr,
-                           (uint32_t*)nullptr, work_counter, wsid, jobs, n_jobs);
-    }
-    hipError_t e = hipGetLastError();
+    const hipError_t e = launch_k_walk<true>(cls == PLAN_WALKC8, walk_plan_waves(BLIND_JOB_CAP), m, pl, jb, stack_rows, rd, CallResults{}, work_counter, jobs, n_jobs, stream);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_finalize_jobs, dim3((BLIND_CHUNKED_READS + 255) / 256), dim3(256), 0, stream, m, clist, 0u, jb,
-                       best_bfs_j, score, num_best, flags, n_class);
+                       out.best_bfs_j, out.score, out.num_best, out.flags, n_class);
     return hipGetLastError();
 }
 

@@ -56,11 +56,10 @@ __global__ __launch_bounds__(64 * WW_WAVES) void k_walk_wave(DevMAT m, const uin
                              flags, work_counter, wsid);
 }
 
-hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_t* count, uint32_t n_reads, const uint32_t* d_read_off,
-                            const uint32_t* d_read_word, const int32_t* root_score, uint32_t* best_bfs_j, int32_t* score, uint32_t* num_best,
-                            uint32_t* flags, unsigned long long* work_counter, const uint32_t* wsid, hipStream_t stream) {
-    hipLaunchKernelGGL(k_walk_wave, dim3(WW_WGS), dim3(64 * WW_WAVES), 0, stream, m, list, count, n_reads, d_read_off, d_read_word, root_score,
-                       best_bfs_j, score, num_best, flags, work_counter, wsid);
+hipError_t launch_walk_wave(const DevMAT& m, const uint32_t* list, const uint32_t* count, uint32_t n_reads, const CallReads& rd, const CallResults& out,
+                            unsigned long long* work_counter, hipStream_t stream) {
+    hipLaunchKernelGGL(k_walk_wave, dim3(WW_WGS), dim3(64 * WW_WAVES), 0, stream, m, list, count, n_reads, rd.off, rd.word, rd.root_score,
+                       out.best_bfs_j, out.score, out.num_best, out.flags, work_counter, rd.wsid);
     return hipGetLastError();
 }
 
