@@ -19,4 +19,6 @@ rc = lib.wepp_debug_route_stats(out)
 v = list(out)
 n = max(v[9], 1)
 names = ["prologue", "offsets+words", "A: counts, root", "A: tree-wide stream", "A: window crown", "A: first loads", "B: class, plan, counters", "lists", "epilogue"]
-print("launches", v[9], {nm: round(v[i] / n, 1) for i, nm in enumerate(names)}, "ticks per launch (s_memtime)")
+stats = {nm: round(v[i] / n, 1) for i, nm in enumerate(names)}
+stats["stores"] = round(v[10] / n, 1)      # (stamp 10: the deferred stores of tools/variants/route_deferred_stores.patch; 0 otherwise)
+print("launches", v[9], stats, "ticks per launch (s_memtime)")

@@ -289,6 +289,8 @@ static_assert(sizeof(WinPlans) <= 3584, "the window plans travel as a kernel arg
 constexpr uint32_t ROUTE_BLOCKS = WEPP_ROUTE_BLOCKS;    // grid of k_route / k_scatter (contiguous slices of the reads); 1024 blocks: route
                                           // 30 -> 22 us but the per-block prefix over earlier blocks in k_scatter 29 -> 92 us
 constexpr uint32_t ROUTE_THREADS = 1024;  // 16 waves per CU: the per-read chains of dependent loads overlap
+constexpr uint32_t ROUTE_STAGED_WORDS = 4;  // words of a read, and routing words of their positions, k_route requests together and
+                                            // keeps in registers; entries beyond them are loaded where they are used
 
 // route: tier of every read + per-(block, tier) counts and per-tier max entries; also clears tier_info_next,
 // the counters the next call will use (they must be zero before its k_route)

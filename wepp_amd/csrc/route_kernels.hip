@@ -25,6 +25,10 @@ __device__ unsigned long long g_route_stats[16];
 #define ROUTE_STAMP(i)
 #define ROUTE_STAMP_NW(i)
 #endif
+// the end of a group of loads requested together: the values are consumed HERE, all of them, so the compiler neither
+// moves a load of the group behind a guard of its first use nor waits for one of them in the middle of the group
+#define ROUTE_LOADS_DONE_4(a, b, c, d) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d))
+#define ROUTE_LOADS_DONE_8(a, b, c, d, e, f, g, h) asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "+v"(g), "+v"(h))
 
 // -----------------------------------------------------------------------------
 // k_route_tables: k_route's routing tables (device_mat.hpp: RouteTables), one block, once per uploaded tree -- until
@@ -123,35 +127,62 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
     const uint32_t* __restrict__ ar_pos = m.rt_pos;
     const uint32_t root_w0 = m.node_woff[0], root_w1 = m.node_woff[1];
     const bool use_tabs = rt.tab_ok != 0;
-    // four reads per thread and round: their offsets, then their first two words, are requested together
-    // (one read after the other, every read cost its thread three memory round trips in a row)
+    // four reads per thread and round, and every phase of a round requests its loads for all four before it uses any:
+    // the offsets, the first SW words of every read, the routing words of those words' positions.  (One read after the
+    // other, and one load after the other, every one of them was a memory round trip of its own in the thread's chain.)
+    // Entries from the SW-th on are loaded where they are used: one read in 300 of a sequencing run has any.
+    constexpr uint32_t SW = ROUTE_STAGED_WORDS;
     const uint32_t lane = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     // (every thread of the block runs the same number of rounds: the walkers' list slots are reserved per block and round)
     for (uint32_t rbase = lo; rbase < hi; rbase += 4 * blockDim.x) {
       const uint32_t r0 = rbase + threadIdx.x;
-      uint32_t so4[4], k4[4], fw[4][2];
+      uint32_t so4[4], k4[4], fw[4][SW];
       uint32_t app4[4] = {0, 0, 0, 0}, aslot4[4] = {0, 0, 0, 0};     // plain walk class + 1 and slot among the block's walkers of the class
       uint32_t cj4[4] = {0, 0, 0, 0}, cjs4[4] = {0, 0, 0, 0}, cls4[4] = {0, 0, 0, 0}, cnj4[4] = {0, 0, 0, 0};   // chunked class + 1, job / list slot in the block, jobs
       uint32_t ww4[4] = {0, 0, 0, 0};                                   // slot + 1 among the block's wave-per-read reads
+      {
+          // (a thread without a read asks for the block's last read's offsets: no guard around the loads, whose region
+          // would end in a wait of its own; read_off[hi] is the last entry read, and hi <= n_reads)
+          uint32_t o0[4], o1[4];
 #pragma unroll
-      for (uint32_t u = 0; u < 4; u++) {
-          const uint32_t r = r0 + u * blockDim.x;
-          so4[u] = r < hi ? read_off[r] : 0u;
-          k4[u] = r < hi ? read_off[r + 1] - so4[u] : 0u;
+          for (uint32_t u = 0; u < 4; u++) {
+              const uint32_t rc = min(r0 + u * blockDim.x, hi - 1u);
+              o0[u] = read_off[rc];
+              o1[u] = read_off[rc + 1];
+          }
+          ROUTE_LOADS_DONE_8(o0[0], o1[0], o0[1], o1[1], o0[2], o1[2], o0[3], o1[3]);
+#pragma unroll
+          for (uint32_t u = 0; u < 4; u++) {
+              const bool valid = r0 + u * blockDim.x < hi;
+              so4[u] = valid ? o0[u] : 0u;
+              k4[u] = valid ? o1[u] - o0[u] : 0u;
+          }
       }
+      // word j of a read is loaded only where the read has one.  (A word not loaded is "any value" until the select
+      // behind the group makes it 0: a 0 merged with the loaded value inside the guard is a copy there, and a wait in
+      // front of the copy -- sixteen round trips in a row.)
 #pragma unroll
       for (uint32_t u = 0; u < 4; u++)
 #pragma unroll
-          for (uint32_t j = 0; j < 2; j++) fw[u][j] = k4[u] > j ? read_word[so4[u] + j] : 0u;
-      ROUTE_STAMP(1);    // offsets and first words
+          for (uint32_t j = 0; j < SW; j++) {
+              fw[u][j] = __builtin_nondeterministic_value(fw[u][j]);
+              if (k4[u] > j) fw[u][j] = read_word[so4[u] + j];
+          }
+      static_assert(SW == 4, "the marker below names the four staged words of a read");
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) ROUTE_LOADS_DONE_4(fw[u][0], fw[u][1], fw[u][2], fw[u][3]);
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++)
+#pragma unroll
+          for (uint32_t j = 0; j < SW; j++) fw[u][j] = k4[u] > j ? fw[u][j] : 0u;
+      ROUTE_STAMP(1);    // offsets and staged words
       // ---- phase A, the four reads one after the other: root score, tree-wide stream, window crown -- words and LDS
-      // tables only -- and the loads the classification below starts with (the list heads and nesting depths of the
-      // read's first two positions in the stream it will most likely walk), requested for all four before any is used:
-      // read by read, every read cost its thread a memory round trip of its own, one after the other
+      // tables only -- and then, for all four together, the loads the classification below starts with (the routing
+      // words of the staged positions in the stream the read will most likely walk)
       int c4[4] = {0, 0, 0, 0};
       uint32_t nh4[4] = {0, 0, 0, 0}, t4[4] = {0, 0, 0, 0}, sid4[4] = {NONE, NONE, NONE, NONE}, wi4[4] = {0, 0, 0, 0}, inwin4[4] = {0, 0, 0, 0};
-      uint32_t pre_w[4][2] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+      uint32_t pre_w[4][SW];
 #pragma unroll
       for (uint32_t u = 0; u < 4; u++) {
         const uint32_t r = r0 + u * blockDim.x;
@@ -159,17 +190,18 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
         if (r < hi) {
             int c = 0;
             auto count = [&](uint32_t sw) { if (!rw_missing(sw)) c += ((rw_mut(sw) & rw_ref(sw)) == 0) ? 1 : 0; };
-            if (k > 0) count(fw[u][0]);
-            if (k > 1) count(fw[u][1]);
-            for (uint32_t j = 2; j < k; j++) count(read_word[so + j]);
+#pragma unroll
+            for (uint32_t j = 0; j < SW; j++)
+                if (k > j) count(fw[u][j]);
+            for (uint32_t j = SW; j < k; j++) count(read_word[so + j]);
             nh4[u] = (uint32_t)c;              // entries whose alleles exclude their reference base (seed_kernels.hip)
             for (uint32_t w = root_w0; w < root_w1; w++) {   // the root's own mutations
                 const uint32_t tw = m.words[w];
                 uint32_t sw = NONE;
-                if (k <= 2) {
-                    if (k > 0 && w_pos(fw[u][0]) == w_pos(tw)) sw = fw[u][0];
-                    if (k > 1 && w_pos(fw[u][1]) == w_pos(tw)) sw = fw[u][1];
-                } else sw = find_entry(read_word, so, k, w_pos(tw));
+#pragma unroll
+                for (uint32_t j = 0; j < SW; j++)
+                    if (k > j && w_pos(fw[u][j]) == w_pos(tw)) sw = fw[u][j];
+                if (k > SW && sw == NONE) sw = find_entry(read_word, so + SW, k - SW, w_pos(tw));      // (positions are sorted and unique)
                 if (sw != NONE) c += enter_delta(tw, sw);
             }
             c4[u] = c;
@@ -187,7 +219,12 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
             // a read inside one genome window: the window crown its ROOT score admits (flatmat.hpp: wcrowns) holds
             // every node that can win or tie -- far fewer than the tree-wide crown of theta = root score + |S|
             if (use_crowns && k > 0) {
-                const uint32_t p_lo = w_pos(fw[u][0]), p_hi = w_pos(k > 2 ? read_word[so + k - 1] : k == 2 ? fw[u][1] : fw[u][0]);
+                uint32_t last = fw[u][0];      // the read's last word: a staged one unless it lists more than SW
+#pragma unroll
+                for (uint32_t j = 1; j < SW; j++)
+                    if (k > j) last = fw[u][j];
+                if (k > SW) last = read_word[so + k - 1];
+                const uint32_t p_lo = w_pos(fw[u][0]), p_hi = w_pos(last);
                 const uint32_t wi = p_lo / WIN_STRIDE;
                 wi4[u] = wi;
                 inwin4[u] = p_hi < wi * WIN_STRIDE + WIN_SIZE ? 1u : 0u;      // all listed positions inside genome window wi
@@ -205,15 +242,17 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
                 }
             }
             ROUTE_STAMP_NW(4);  // window crown
-            if (walk_max_events && k <= WALK16_K) {
-                const uint32_t tab = sid4[u] != NONE ? sid4[u] : m.tw_base + t;
-#pragma unroll
-                for (uint32_t j = 0; j < 2; j++) {
-                    const uint32_t p = w_pos(fw[u][j]);
-                    if (j < k && p <= m.max_pos) pre_w[u][j] = ar_pos[rt_head[tab] + p];
-                }
-            }
         }
+      }
+#pragma unroll
+      for (uint32_t u = 0; u < 4; u++) {
+          const bool walks = r0 + u * blockDim.x < hi && walk_max_events && k4[u] <= WALK16_K;
+          const uint32_t* pre_pos = ar_pos + rt_head[sid4[u] != NONE ? sid4[u] : m.tw_base + t4[u]];
+#pragma unroll
+          for (uint32_t j = 0; j < SW; j++) {
+              const uint32_t p = w_pos(fw[u][j]);
+              pre_w[u][j] = walks && j < k4[u] && p <= m.max_pos ? pre_pos[p] : 0u;
+          }
       }
       ROUTE_STAMP(5);    // the first loads of the classification
       // ---- phase B: class and plan of every read ----
@@ -242,19 +281,33 @@ __global__ __launch_bounds__(ROUTE_THREADS) void k_route(DevMAT m, const uint32_
         auto classify = [&](uint32_t tab, uint32_t& nj_out, uint32_t& open_out, uint32_t& ev_out) -> uint32_t {
             const uint32_t* ix_pos = ar_pos + rt_head[tab];
             uint32_t open_max = 0, events = 0, longest = 0;
-            for (uint32_t j = 0; j < k; j++) {
-                const uint32_t p = w_pos(j == 0 ? fw[u][0] : j == 1 ? fw[u][1] : read_word[so + j]);
-                if (p <= m.max_pos) {
-                    uint32_t nest, len;
-                    if (!rt_pos_unpack(j < 2 && tab == pre_tab ? (j ? pre_w[u][1] : pre_w[u][0]) : ix_pos[p], len, nest)) {
-                        // (a list longer than the field holds: the exact length from its heads; every list ends in a sentinel)
-                        const IxHead* ix_head = m.walks[WC_SLOT].ix_head + rt_head[tab];
-                        len = ix_head[p + 1].off - ix_head[p].off - 1u;
-                    }
-                    open_max += nest;
-                    events += len;
-                    longest = max(longest, len);
+            auto take = [&](uint32_t p, uint32_t word) {
+                uint32_t nest, len;
+                if (!rt_pos_unpack(word, len, nest)) {
+                    // (a list longer than the field holds: the exact length from its heads; every list ends in a sentinel)
+                    const IxHead* ix_head = m.walks[WC_SLOT].ix_head + rt_head[tab];
+                    len = ix_head[p + 1].off - ix_head[p].off - 1u;
                 }
+                open_max += nest;
+                events += len;
+                longest = max(longest, len);
+            };
+            // the staged positions: phase A's words where this is the stream it asked about, else (a window crown
+            // refused) the stream's own, again requested together
+            uint32_t sw4[SW];
+#pragma unroll
+            for (uint32_t j = 0; j < SW; j++) {
+                const uint32_t p = w_pos(fw[u][j]);
+                sw4[j] = tab == pre_tab ? pre_w[u][j] : (j < k && p <= m.max_pos) ? ix_pos[p] : 0u;
+            }
+#pragma unroll
+            for (uint32_t j = 0; j < SW; j++) {
+                const uint32_t p = w_pos(fw[u][j]);
+                if (j < k && p <= m.max_pos) take(p, sw4[j]);
+            }
+            for (uint32_t j = SW; j < k; j++) {
+                const uint32_t p = w_pos(read_word[so + j]);
+                if (p <= m.max_pos) take(p, ix_pos[p]);
             }
             open_out = open_max;
             ev_out = events;
