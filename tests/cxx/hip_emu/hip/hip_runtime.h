@@ -25,6 +25,7 @@ extern unsigned char g_emu_lds[];
 #define HIP_DYNAMIC_SHARED(type, var) type* var = (type*)g_emu_lds;
 struct dim3 { unsigned x, y, z; dim3(unsigned a = 1, unsigned b = 1, unsigned c = 1) : x(a), y(b), z(c) {} };
 struct uint2 { uint32_t x, y; };
+struct int4 { int x, y, z, w; };
 inline uint2 make_uint2(uint32_t a, uint32_t b) { return uint2{a, b}; }
 typedef int hipError_t; typedef void* hipStream_t; typedef void* hipEvent_t;
 constexpr int hipSuccess = 0, hipErrorOutOfMemory = 2;

@@ -41,7 +41,7 @@ extern "C" int wepp_mat_set_clades(wepp_mat_t* mat, uint32_t n_columns, const ui
         return set_error(WEPP_ELIMIT, std::to_string(n_columns) + " annotation columns, at most " + std::to_string(CLADE_MAX_COLUMNS));
     HIP_TRY(hipSetDevice(mat->device));
     if (n_columns == 0) {
-        if (mat->clade_tab.ptr) { HIP_TRY(hipFree(mat->clade_tab.ptr)); mat->clade_tab.ptr = nullptr; }
+        mat->clade_tab.reset();
         mat->clade_columns = 0;
         return WEPP_OK;
     }
@@ -52,15 +52,7 @@ extern "C" int wepp_mat_set_clades(wepp_mat_t* mat, uint32_t n_columns, const ui
     for (uint32_t d = 1; d < N; d++)
         if (parent_dfs[d] >= d) return set_error(WEPP_EDEVICE, "parent_dfs is not a pre-order");
     clade_build_tables(N, n_columns, parent_dfs.data(), mat->dfs2id.data(), clade_id, undefined_id, tab);
-    uint32_t* d_tab = nullptr;
-    {
-        hipError_t e = hipMalloc((void**)&d_tab, tab.size() * 4);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-        e = hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d_tab); return hip_fail(e, "clade tables"); }
-    }
-    if (mat->clade_tab.ptr) (void)hipFree(mat->clade_tab.ptr);
-    mat->clade_tab.ptr = d_tab;
+    WEPP_TRY(upload_whole(mat->clade_tab, tab.data(), tab.size(), "clade tables"));
     mat->clade_columns = n_columns;
     return WEPP_OK;
 }

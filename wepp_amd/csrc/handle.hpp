@@ -60,7 +60,30 @@ template <typename T = void> struct DevMem : NoCopy {
         ptr = nullptr;
     }
     operator T*() const { return ptr; }
+    // gives back what it holds and takes `bytes` bytes, at least 16 / `count` elements (bytes for T = void)
+    int alloc_bytes(size_t bytes, const char* what) {
+        reset();
+        bytes = std::max<size_t>(bytes, 16);
+        const hipError_t e = pinned ? hipHostMalloc((void**)&ptr, bytes) : hipMalloc((void**)&ptr, bytes);
+        if (e == hipSuccess) return WEPP_OK;
+        ptr = nullptr;
+        return set_error(WEPP_ENOMEM, std::string(pinned ? "hipHostMalloc " : "hipMalloc ") + what + ": " + hipGetErrorString(e));
+    }
+    int alloc(size_t count, const char* what) { return alloc_bytes(count * sizeof(std::conditional_t<std::is_void_v<T>, char, T>), what); }
 };
+
+// A table an owner keeps between calls is made whole or not at all: filled in a block of its own and swapped in, the
+// block it replaces freed behind the swap.  On any failure `dst` is as it was: an owner is null or holds a table
+// that was written completely.
+template <typename T>
+inline int upload_whole(DevMem<T>& dst, const T* src, size_t count, const char* what) {
+    DevMem<T> fresh(dst.pinned);
+    WEPP_TRY(fresh.alloc(count, what));
+    const hipError_t e = count ? hipMemcpy(fresh, src, count * sizeof(T), hipMemcpyHostToDevice) : hipSuccess;
+    if (e != hipSuccess) return set_error(WEPP_EDEVICE, std::string("upload of ") + what + ": " + hipGetErrorString(e));
+    std::swap(dst.ptr, fresh.ptr);
+    return WEPP_OK;
+}
 
 // A grow-only buffer of a handle, in device or in pinned host memory: kept while it holds `need` bytes; else freed --
 // behind a device-wide synchronisation: work in flight may still use it, hipFree waits for the device anyway, and a
@@ -70,14 +93,10 @@ template <typename T = void> struct GrowBuf : DevMem<T> {
     using DevMem<T>::DevMem;
     int reserve(size_t need, size_t slack, const char* what) {
         if (need <= bytes) return WEPP_OK;
-        if (this->ptr) {
-            HIP_TRY(hipDeviceSynchronize());
-            this->reset();
-            bytes = 0;
-        }
+        if (this->ptr) HIP_TRY(hipDeviceSynchronize());
+        bytes = 0;
         const size_t want = need + need / slack;
-        const hipError_t e = this->pinned ? hipHostMalloc((void**)&this->ptr, want) : hipMalloc((void**)&this->ptr, want);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string(this->pinned ? "hipHostMalloc " : "hipMalloc ") + what + ": " + hipGetErrorString(e));
+        WEPP_TRY(this->alloc_bytes(want, what));
         bytes = want;
         return WEPP_OK;
     }

@@ -44,13 +44,8 @@ int prepare_handle(wepp_mat_t* mat) {
     for (uint32_t d = 0; d < N; d++) end[d] = d + 1;
     for (uint32_t d = N; d-- > 1;) end[parent[d]] = std::max(end[parent[d]], end[d]);
     // (the handle takes the block once it is filled: a call that fails here leaves none, and the next one tries again)
-    DevMem<uint32_t> d_end;
-    const size_t bytes = std::max<size_t>((size_t)N * 4, 16);
-    const hipError_t e = hipMalloc((void**)&d_end.ptr, bytes);
-    if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc: ") + hipGetErrorString(e));
-    HIP_TRY(hipMemcpy(d_end, end.data(), (size_t)N * 4, hipMemcpyHostToDevice));
-    std::swap(mat->nbr_dfs_end.ptr, d_end.ptr);
-    mat->stats.device_bytes += bytes;
+    WEPP_TRY(upload_whole(mat->nbr_dfs_end, end.data(), N, "dfs_end"));
+    mat->stats.device_bytes += std::max<size_t>((size_t)N * 4, 16);
     return WEPP_OK;
 }
 

@@ -257,18 +257,16 @@ extern "C" int wepp_place_batch(wepp_mat_t* mat, const uint32_t* read_off, const
     for (uint32_t t = 0; t < n_copy; t++)
         if (copy_err[t] != hipSuccess) return hip_fail(copy_err[t], "D2H copy of the results");
     if (per_node_scores) {
-        int32_t* d_pns = nullptr;
+        DevMem<int32_t> d_pns;
         const size_t nb = (size_t)n_reads * mat->dev.N * sizeof(int32_t);
-        hipError_t e = hipMalloc((void**)&d_pns, nb);
-        if (e != hipSuccess) return set_error(WEPP_ENOMEM, std::string("hipMalloc per_node_scores: ") + hipGetErrorString(e));
+        WEPP_TRY(d_pns.alloc((size_t)n_reads * mat->dev.N, "per_node_scores"));
         if (mat->tun.debug_plans) {
             const DevStream& full = mat->streams.back();
             const Pass2Chunks ch = pass2_chunks(n_reads, full.NB, full.ncp, full.cp_stride, false);
             fprintf(stderr, "[scores] n_reads=%u nchunks=%u bpc=%u\n", n_reads, ch.nchunks, ch.bpc);
         }
-        e = launch_scores(mat->dev, mat->streams.back(), d_off, d_word, n_reads, d_pns, nullptr);   // (everything above has been synchronised)
+        hipError_t e = launch_scores(mat->dev, mat->streams.back(), d_off, d_word, n_reads, d_pns, nullptr);   // (everything above has been synchronised)
         if (e == hipSuccess) e = hipMemcpy(per_node_scores, d_pns, nb, hipMemcpyDeviceToHost);
-        (void)hipFree(d_pns);
         if (e != hipSuccess) return hip_fail(e, "per-node score kernel");
     }
     if (dbg_time) {
